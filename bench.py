@@ -22,6 +22,12 @@ edge-file ingestion and BipartitenessCheck (bench_rows.py).
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 under torch.distributed.run.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the
+roofline of the fold launches timed inside the last step, the timed path's final checksum).
+--full adds what takes runs of its own: the close's kernel time (one more untimed step), the
+cpu_baseline (the C oracle on the host), the comparison of the final checksum with the C oracle's
+fixture. --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -83,7 +89,14 @@ def parse():
                          "(gs_cc_emit_delta_async: the copy of window w overlaps the fold of window w+1)")
     ap.add_argument("--emit-sync", action="store_true",
                     help="with --emit-host: the blocking gs_cc_emit_delta per window instead")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need and takes runs of its own: the close's "
+                         "kernel time (one more untimed step), the cpu_baseline, the comparison of the final "
+                         "checksum with the C oracle's fixture")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline out")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64, at most 64 MB in all: a larger array is cut to a fixed seeded sample)")
     ap.add_argument("--verify", action="store_true", help="check final labels with an independent torch CC "
                     "(multi-rank: rank 0 regenerates the whole global stream; small scales only)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
@@ -182,7 +195,7 @@ def main():
     os.dup2(2, 1)
     if a.kind in ("parse", "bip", "parse_file"):  # SURVEY.md 8(f) rows, one GPU
         import bench_rows
-        {"parse": bench_rows.run_parse, "bip": bench_rows.run_bip, "parse_file": bench_rows.run_parse_file}[a.kind](a, out)
+        {"parse": bench_rows.run_parse, "bip": bench_rows.run_bip, "parse_file": bench_rows.run_parse_file}[a.kind](a, out, dump_outputs)
         return
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -322,13 +335,24 @@ def main():
     merge_ms, _ = ds.kernel_time(GS_K_MERGE)
     export_ms, _ = ds.kernel_time(GS_K_EXPORT)
     ds.timing(False)
-    # one more (untimed) step: the close's kernel time
-    ds.timing(GS_TIMING_MASK | (1 << GS_K_COMPRESS))
-    ds.reset()
-    for w in range(nwin):
-        window(w)
-    comp_ms, comp_n = ds.kernel_time(GS_K_COMPRESS)
-    ds.timing(False)
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last step: the last window's canonical
+        # emission (label per vertex, -1 = not seen), its counts and its checksum (two 32-bit halves)
+        lab = torch.empty(V, dtype=idt, device=dev)
+        ds.dense(out=lab)
+        dump_outputs(a.dump_outputs, {
+            "labels": lab,
+            "summary": [final_sum[1], final_sum[2], (final_sum[0] >> 32) & 0xFFFFFFFF, final_sum[0] & 0xFFFFFFFF]})
+        del lab
+    comp_ms = comp_n = None
+    if a.full:
+        # one more (untimed) step: the close's kernel time
+        ds.timing(GS_TIMING_MASK | (1 << GS_K_COMPRESS))
+        ds.reset()
+        for w in range(nwin):
+            window(w)
+        comp_ms, comp_n = ds.kernel_time(GS_K_COMPRESS)
+        ds.timing(False)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if a.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -415,7 +439,7 @@ def main():
         step_b = per_edge * E_glob                                  # SURVEY 8(d) edge term per step
         step_gbs = step_b * a.steps / elapsed / 1e9
         nv, nc = ds.stats()
-        fx_path, fx_last = fixture_last(a, world)
+        fx_path, fx_last = fixture_last(a, world) if a.full else (None, None)
         line = {
             "metric": METRIC,
             "value": total_edges / elapsed,
@@ -483,8 +507,6 @@ def main():
             },
             "kernels": {
                 "fold_share": (young_ms + ring_ms) / (elapsed / a.steps * 1e3),   # timed: the last step's folds
-                "compress_ms_per_window": comp_ms / max(comp_n, 1),
-                "compress_share": comp_ms / (elapsed / a.steps * 1e3),
             },
             "library": os.path.relpath(LIB_PATH, ROOT),
             "final_vertices": nv,
@@ -496,12 +518,17 @@ def main():
                               "and component counts of the last window of the last timed step vs the C oracle's "
                               "fixture for that window"},
         }
+        if a.full:
+            line["kernels"]["compress_ms_per_window"] = comp_ms / max(comp_n, 1)
+            line["kernels"]["compress_share"] = comp_ms / (elapsed / a.steps * 1e3)
+        else:                                        # (no fixture comparison in a plain run)
+            del line["final_checksum_vs_fixture"]
         if world > 1:                                # rank 0's side of the exchange
             overflows = None
             if comm is not None:
                 _, _, sent, recv, nex, overflows = comm.info()
             else:
-                sent, recv, nex = tree.bytes_sent, tree.bytes_recv, (a.warmup + a.steps + 1) * nwin
+                sent, recv, nex = tree.bytes_sent, tree.bytes_recv, (a.warmup + a.steps + (1 if a.full else 0)) * nwin
             line["exchange"] = {
                 "merge": a.merge, "transport": "RCCL (C ABI)" if comm is not None else "gloo (Python)",
                 "merge_fold_ms_per_window": merge_ms / max(folds, 1),
@@ -520,7 +547,7 @@ def main():
             line["verify"] = verify
         if latency is not None:
             line["window_latency"] = latency
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             log("timed region done (%.1f ms/step); cpu baseline..." % (elapsed / a.steps * 1e3))
             line["cpu_baseline"] = cpu_baseline(a, ds, window, src, dst, W_rank, nwin)
         print(json.dumps(line), file=out, flush=True)
@@ -531,6 +558,23 @@ def main():
         comm.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: every array as path/<name>.npy in float64 (exact for ids and counts, all below
+    2^53), at most 64 MB in all. An array over its share of that is cut to a fixed sample: sorted
+    indices drawn with replacement from numpy's RandomState(seed), the same from run to run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = min(1 << 22, (48 << 20) // 8 // len(arrays))          # elements per array
+    for name, x in arrays.items():
+        if torch.is_tensor(x):
+            x = x.reshape(-1)
+            if x.numel() > share:
+                idx = np.sort(np.random.RandomState(seed).randint(0, x.numel(), share))
+                x = x[torch.from_numpy(idx).to(x.device)]
+            x = x.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.asarray(x, dtype=np.float64))
 
 
 def fixture_last(a, world: int):

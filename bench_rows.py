@@ -9,9 +9,10 @@
                      stream (RMAT endpoints a, b -> 2a, 2b + 1) folded window by window, each
                      window closed (the Merger's emission), like the connected-components step.
 
-Each prints bench.py's one JSON line (value, roofline of the whole call / step, cpu_baseline of
-the oracle restatement on the host, a verification of the outputs). The oracle (oracle/) is used
-only as the checker and as cpu_baseline.
+Each prints bench.py's one JSON line (value, roofline of the whole call / step, a verification of
+the outputs; with --full the cpu_baseline of the oracle restatement on the host). The oracle
+(oracle/) is used only as the checker and as cpu_baseline. --dump-outputs DIR writes the last timed
+step's outputs through bench.py's dump_outputs.
 """
 from __future__ import annotations
 
@@ -61,7 +62,7 @@ def _line(a, metric, value, unit, ms, workload, extra):
     return line
 
 
-def run_parse(a, out):
+def run_parse(a, out, dump=None):
     import torch
     import gsgpu  # noqa: F401  (loads libgsgpu after torch)
     from gsgpu import gen
@@ -92,6 +93,8 @@ def run_parse(a, out):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / a.steps
     ok = int(got.value) == n and bool(torch.equal(ps, s.to(torch.int64))) and bool(torch.equal(pd, d.to(torch.int64)))
+    if a.dump_outputs:                                     # the last call's outputs: ids and line count
+        dump(a.dump_outputs, {"src": ps, "dst": pd, "lines": [int(got.value)]})
     alg = nbytes + 16 * n                                  # text read once + int64 (src, dst) written
     achieved = alg / (ms * 1e-3) / 1e9
     extra = {"dtype": "u8 text -> int64",
@@ -103,7 +106,7 @@ def run_parse(a, out):
                                         "sync for the line count included); kernels in profiles/r04_rows_*"},
              "text_bytes": nbytes, "text_GBps": nbytes / (ms * 1e-3) / 1e9,
              "verify": {"lines": int(got.value), "equal_to_generated_ids": ok}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from pyoracle import coracle
         host = text.cpu().numpy().tobytes()
@@ -117,7 +120,7 @@ def run_parse(a, out):
                                       "text": "one 'src dst\\n' line per edge, decimal"}, extra)), file=out, flush=True)
 
 
-def run_parse_file(a, out):
+def run_parse_file(a, out, dump=None):
     """Streaming edge-file ingestion end to end (gs_cc_fold_text): the text of
     BASELINE config 2's stream (RMAT-20 EF16, 2^24 "src dst\\n" lines) in PINNED host memory, moved
     in 64 MiB chunks over PCIe through the double-buffered staging, parsed on the device into the
@@ -155,6 +158,12 @@ def run_parse_file(a, out):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / a.steps
     final = ds.checksum()
+    if a.dump_outputs:                                     # the last step's (edges, windows) and final emission
+        lab = torch.empty(V, dtype=torch.int32, device=dev)
+        ds.dense(out=lab)
+        dump(a.dump_outputs, {"labels": lab, "summary": [res["ew"][0], res["ew"][1], final[1], final[2],
+                                                         (final[0] >> 32) & 0xFFFFFFFF, final[0] & 0xFFFFFFFF]})
+        del lab
     # the PCIe ceiling of this path: one pinned -> device copy of the whole text
     dbuf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
@@ -175,7 +184,7 @@ def run_parse_file(a, out):
              "text_bytes": nbytes,
              "verify": {"edges": res["ew"][0], "windows": res["ew"][1], "final_checksum": str(final[0]),
                         "final_vertices": final[1], "final_components": final[2]}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from pyoracle import EMIT_FLATTEN, coracle
         o = coracle()
@@ -197,7 +206,7 @@ def run_parse_file(a, out):
                        "chunk_bytes": 64 << 20, "windows": (n + W - 1) // W}, extra)), file=out, flush=True)
 
 
-def run_bip(a, out):
+def run_bip(a, out, dump=None):
     import torch
     import gsgpu
     from gsgpu import gen
@@ -230,6 +239,10 @@ def run_bip(a, out):
     torch.cuda.synchronize()
     ms = (time.perf_counter() - t0) * 1e3 / a.steps
     ok_b, nv, nc = c.status()
+    if a.dump_outputs:                                     # the last step's summary: (vertex, key, sign) entries
+        pv, pk, psg = c.pairs()
+        dump(a.dump_outputs, {"vertices": torch.from_numpy(pv), "keys": torch.from_numpy(pk),
+                              "signs": torch.from_numpy(psg.astype("int64")), "status": [int(ok_b), nv, nc]})
     ds = gsgpu.DisjointSet(cap, id_bits=32, stream=st)     # the same graph's components (check)
     ds.fold(s, d)
     ds.close_window()
@@ -244,7 +257,7 @@ def run_bip(a, out):
                                         "fold and close)"},
              "verify": {"bipartite": bool(ok_b), "vertices": nv, "components": nc,
                         "equal_to_cc_counts": (nv, nc) == (cv, cc)}}
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from bipartite import literal_run
         from pyoracle import coracle

@@ -35,6 +35,23 @@ def test_prefilter_share0_balances_rank0():
     assert bench.prefilter_share0(8) == 0.0                 # rank 0 folds no slice of its own
 
 
+def test_dump_outputs_is_float64_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: float64 files, small arrays whole, a large one cut to the same sample of its
+    own entries on every call, 64 MB in all at the most."""
+    import numpy as np
+    import torch
+    big = torch.arange(1 << 23, dtype=torch.int32) * 3 - 1
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"labels": big, "summary": [7, 1 << 31, (1 << 32) - 1]})
+    la, lb = np.load(tmp_path / "a" / "labels.npy"), np.load(tmp_path / "b" / "labels.npy")
+    assert la.dtype == np.float64 and 0 < la.size < big.numel() and np.array_equal(la, lb)
+    assert np.all((la + 1) % 3 == 0) and np.all(np.diff(la) >= 0) and la.max() > 3 * (1 << 22)
+    s = np.load(tmp_path / "a" / "summary.npy")
+    assert s.dtype == np.float64 and s.tolist() == [7.0, float(1 << 31), float((1 << 32) - 1)]
+    total = sum(f.stat().st_size for f in (tmp_path / "a").iterdir())
+    assert total <= 64 * 1000 * 1000
+
+
 @pytest.mark.parametrize("world", [1, 2, 4, 8])
 def test_even_strong_layout(world):
     a = _A()

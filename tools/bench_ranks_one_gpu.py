@@ -7,9 +7,10 @@ takes them for separate hosts and connects them through its network transport ov
 
 The timings of this transport (host sockets, P ranks sharing one GPU) mean nothing; what this
 checks is that the multi-rank bench runs end to end over RCCL and that rank 0's timed emission
-equals the fixture (`final_checksum_vs_fixture`) and, with --verify, an independent torch CC.
+equals the fixture (`final_checksum_vs_fixture`, under bench.py's --full) and, with --verify, an
+independent torch CC.
 
-  python tools/bench_ranks_one_gpu.py --ranks 4 -- --steps 1 --warmup 0 --no-cpu-baseline --verify
+  python tools/bench_ranks_one_gpu.py --ranks 4 -- --steps 1 --warmup 0 --full --no-cpu-baseline --verify
 """
 from __future__ import annotations
 

@@ -19,7 +19,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/
 rc=$?; echo "smoke rc=$rc"; tail -3 "$OUT/smoke.log"
 if fatal $rc || faulted "$OUT/smoke.log"; then exit 3; fi
 
-timeout -k 10 600 python -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -3 "$OUT/bench.err"
 if [ $rc -ne 0 ]; then exit 3; fi
 
