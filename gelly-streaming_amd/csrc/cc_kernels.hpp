@@ -83,6 +83,13 @@ __device__ __forceinline__ uint32_t make_set(uint32_t* __restrict__ parent, uint
 // per-thread diagnostic counters (GSGPU_FOLD_STATS=1 builds the STATS variant of k_fold)
 struct FoldStats {
     uint32_t early = 0, hooks = 0, casfail = 0, inits = 0;
+    // a thread's counters into the launch's stats words (FoldArgs::stats [2..5]) at its end
+    __device__ __forceinline__ void flush(unsigned long long* stats) const {
+        atomicAdd(&stats[2], (unsigned long long)early);
+        atomicAdd(&stats[3], (unsigned long long)hooks);
+        atomicAdd(&stats[4], (unsigned long long)casfail);
+        atomicAdd(&stats[5], (unsigned long long)inits);
+    }
 };
 
 // hbits (or null): the hooked-root bitmap of a fold before any giant exists (k_compress: the full
@@ -163,7 +170,6 @@ __device__ __forceinline__ uint32_t union_edge(uint32_t* __restrict__ parent, ui
     }
     return kInvalid;
 }
-
 
 // Hook log (GS_CC_TRACK_MARKS): the vertices a partial-summary export carries, appended in
 // launch order. Wave-aggregated: one atomicAdd on the log length per wave call (the active lanes'
@@ -682,97 +688,56 @@ __device__ __forceinline__ void combine_hooks(uint32_t* __restrict__ parent, boo
     pv = x;
 }
 
-template <bool MARK, bool STATS, int EPT>
-__device__ __forceinline__ void union_group(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
-                                            const bool (&ok)[EPT], FoldStats& st) {
-    uint32_t pu[EPT], pv[EPT];
+// Path halving in an edge's root walks, from f.halve: 0 = never, 1 = always; > 1 = for a hashed
+// eighth of the edges (hashed: union_group's rule) or always (the giant paths': f.halve != 0).
+__device__ __forceinline__ bool halve_rule(uint32_t mode, uint32_t u, bool hashed) {
+    return hashed ? (mode == 1 || (mode > 1 && ((u * 0x9E3779B1u) >> 29) == 0)) : mode != 0;
+}
+
+// The unions of one thread's EPT edges, given their parent words. cx[k] != kInvalid: edge k is
+// done, its endpoint cx[k] claimed under the giant root (union_group_g). A logging fold (f.tlog)
+// also puts the edges' first touches, claims included, into the touch log; a pair fold (f.combine)
+// first combines the wave's hooks of one root (combine_hooks); PLAIN (the ring fold) is neither.
+// The hooked vertices go to the hook log (MARK), or to marks_out for the caller to append.
+template <bool MARK, bool STATS, int EPT, bool PLAIN>
+__device__ __forceinline__ void union_tail(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
+                                           const bool (&ok)[EPT], uint32_t (&pu)[EPT], uint32_t (&pv)[EPT],
+                                           const uint32_t (&cx)[EPT], bool hashed, FoldStats& st, uint32_t* marks_out) {
+    uint32_t m[EPT];                                 // marks: a claim's is the claimed vertex
+    bool live[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
-        pu[k] = ok[k] ? f.parent[u[k]] : 0u;
-        pv[k] = ok[k] ? f.parent[v[k]] : 0u;
+        m[k] = cx[k];
+        live[k] = ok[k] && cx[k] == kInvalid;
     }
-    uint32_t m[EPT];
-    if (f.tlog) {                                    // logging fold: first touches into the touch log too
+    if (!PLAIN && f.tlog) {
         NewV nl[EPT];
-#pragma unroll
-        for (int k = 0; k < EPT; ++k)
-            m[k] = ok[k] ? union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st,
-                                                   f.halve == 1 || (f.halve > 1 && ((u[k] * 0x9E3779B1u) >> 29) == 0),
-                                                   f.hbits, &nl[k]) : kInvalid;
         uint32_t t[2 * EPT];
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
+            nl[k].a = cx[k];
+            if (live[k]) m[k] = union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st,
+                                                        halve_rule(f.halve, u[k], hashed), f.hbits, &nl[k]);
             t[2 * k] = nl[k].a;
             t[2 * k + 1] = nl[k].b;
         }
         slot_append<2 * EPT>(f.tlog, f.tcnt, t);
-    } else if (f.combine) {                          // pair folds: combined hooks (combine_hooks)
+    } else if (!PLAIN && f.combine) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
-            const bool halve = f.halve == 1 || (f.halve > 1 && ((u[k] * 0x9E3779B1u) >> 29) == 0);
+            const bool halve = halve_rule(f.halve, u[k], hashed);
             uint32_t cu = u[k], cv = v[k];
             bool skip;
-            combine_hooks(f.parent, halve, ok[k], cu, cv, pu[k], pv[k], skip);
-            m[k] = (ok[k] && !skip) ? union_edge<MARK, STATS>(f.parent, f.sbits, cu, cv, pu[k], pv[k], &st, halve, f.hbits)
-                                    : kInvalid;
+            combine_hooks(f.parent, halve, live[k], cu, cv, pu[k], pv[k], skip);
+            if (live[k] && !skip) m[k] = union_edge<MARK, STATS>(f.parent, f.sbits, cu, cv, pu[k], pv[k], &st, halve, f.hbits);
         }
     } else {
 #pragma unroll
         for (int k = 0; k < EPT; ++k)
-            m[k] = ok[k] ? union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st,
-                                                   f.halve == 1 || (f.halve > 1 && ((u[k] * 0x9E3779B1u) >> 29) == 0),
-                                                   f.hbits) : kInvalid;
+            if (live[k]) m[k] = union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st,
+                                                        halve_rule(f.halve, u[k], hashed), f.hbits);
     }
-    if (MARK) log_append<EPT>(f.mark, f.mark_len, m);
-}
-
-// As union_group, for survivors whose giant flags are known (bit 0: u in the giant, bit 1: v): a
-// giant member x was relabelled to the giant root gR by the last close and is no root (gR is), so
-// its parent word can only have moved to an ancestor of gR since; gR stands in for the parent[x]
-// read (the walk goes on from gR, halving with fetch_min, and the hook CAS decides as for any
-// stale read). Saves one random parent[] gather per survivor with one endpoint in the giant
-// (most survivors of windows 2-12: a first-touched vertex joining the giant). Ring fold only:
-// in the young forest the giant root gR is hooked again and again, and every walk from a stand-in
-// gR then halves a shared word (x = a hub, or gR's own word when the walk starts at gR):
-// one same-address atomic per edge, window 1 1.3 -> 2.7 ms; taking gR itself for a root instead
-// fails every hook CAS on gR's word once it is hooked (14 ms). A/B in profiles/r01_v12.
-// An endpoint outside the giant next to one inside is first claimed straight under gR (below):
-// windows 2-12 -158 us, steady -2.5 us per window (profiles/r02_ab_experiments.txt r02_aa).
-template <bool MARK, bool STATS, int EPT>
-__device__ __forceinline__ void union_group_g(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
-                                              const bool (&ok)[EPT], const uint32_t (&gflag)[EPT], uint32_t gR,
-                                              FoldStats& st, uint32_t* marks_out = nullptr) {
-    uint32_t pu[EPT], pv[EPT];
-    // one endpoint in the giant, the other x > gR: claim x straight under gR with a CAS from
-    // kInvalid instead of gathering parent[x] first. Success = x was never touched, and hanging a
-    // fresh singleton below any giant member (gR < x keeps parent[x] < x) is its union with the
-    // giant; failure returns parent[x], the word the gather would have read.
-    bool claimed[EPT];
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        const bool cu = ok[k] && gflag[k] == 2u && u[k] > gR;      // v in the giant, u outside
-        const bool cv = ok[k] && gflag[k] == 1u && v[k] > gR;      // u in the giant, v outside
-        pu[k] = !ok[k] ? 0u : (gflag[k] & 1u) ? gR : cu ? atomicCAS(&f.parent[u[k]], kInvalid, gR) : f.parent[u[k]];
-        pv[k] = !ok[k] ? 0u : (gflag[k] & 2u) ? gR : cv ? atomicCAS(&f.parent[v[k]], kInvalid, gR) : f.parent[v[k]];
-        claimed[k] = (cu && pu[k] == kInvalid) || (cv && pv[k] == kInvalid);
-    }
-    uint32_t m[EPT];
-#pragma unroll
-    for (int k = 0; k < EPT; ++k) {
-        if (claimed[k]) {
-            const uint32_t x = (gflag[k] == 2u) ? u[k] : v[k];
-            // a claimed vertex is a depth-1 child of gR, the root the next incremental close labels
-            // the giant with: that close only sets its gbits bit (cbits, no parent[] read); a close
-            // that is a full pass reads every parent[] word anyway. Without cbits: the seen bit.
-            if (f.cbits) set_mark(f.cbits, x);
-            else set_seen(f.sbits, x);
-            if (STATS) { ++st.inits; ++st.hooks; }
-            m[k] = MARK ? x : kInvalid;
-        } else {
-            m[k] = ok[k] ? union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st, f.halve != 0, f.hbits) : kInvalid;
-        }
-    }
-    if (MARK && marks_out) {                         // the caller appends them (ring_flush_final)
+    if (MARK && marks_out) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) marks_out[k] = m[k];
     } else if (MARK) {
@@ -780,70 +745,63 @@ __device__ __forceinline__ void union_group_g(const FoldArgs& f, const uint32_t 
     }
 }
 
-// union_group_g for k_fold's small mature folds (f.claim): the same claims and gR stand-ins, plus
-// the touch log of a logging fold (first touches, claims included). A separate copy so that the
-// ring fold's code is not touched.
 template <bool MARK, bool STATS, int EPT>
-__device__ __forceinline__ void union_group_gl(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
-                                               const bool (&ok)[EPT], const uint32_t (&gflag)[EPT], uint32_t gR,
-                                               FoldStats& st) {
-    uint32_t pu[EPT], pv[EPT];
-    bool claimed[EPT];
+__device__ __forceinline__ void union_group(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
+                                            const bool (&ok)[EPT], FoldStats& st) {
+    uint32_t pu[EPT], pv[EPT], cx[EPT];
+#pragma unroll
+    for (int k = 0; k < EPT; ++k) {
+        pu[k] = ok[k] ? f.parent[u[k]] : 0u;
+        pv[k] = ok[k] ? f.parent[v[k]] : 0u;
+        cx[k] = kInvalid;
+    }
+    union_tail<MARK, STATS, EPT, false>(f, u, v, ok, pu, pv, cx, true, st, nullptr);
+}
+
+// As union_group, for survivors whose giant flags are known (bit 0: u in the giant, bit 1: v): a
+// giant member x was relabelled to the giant root gR by the last close and is no root (gR is), so
+// its parent word can only have moved to an ancestor of gR since; gR stands in for the parent[x]
+// read (the walk goes on from gR, halving with fetch_min, and the hook CAS decides as for any
+// stale read). Saves one random parent[] gather per survivor with one endpoint in the giant
+// (most survivors of windows 2-12: a first-touched vertex joining the giant). Mature folds only:
+// in the young forest the giant root gR is hooked again and again, and every walk from a stand-in
+// gR then halves a shared word (x = a hub, or gR's own word when the walk starts at gR):
+// one same-address atomic per edge, window 1 1.3 -> 2.7 ms; taking gR itself for a root instead
+// fails every hook CAS on gR's word once it is hooked (14 ms). A/B in profiles/r01_v12.
+// An endpoint outside the giant next to one inside is first claimed straight under gR (below):
+// windows 2-12 -158 us, steady -2.5 us per window (profiles/r02_ab_experiments.txt r02_aa).
+// RING: k_fold_ring's survivors — plain unions, and a claim sets its cbits bit when the handle has
+// that bitmap. !RING: k_fold's small mature folds (claim) — union_group's tail, and a claim is a
+// first touch like any other: the seen bit, and the touch log of a logging fold.
+template <bool MARK, bool STATS, int EPT, bool RING>
+__device__ __forceinline__ void union_group_g(const FoldArgs& f, const uint32_t (&u)[EPT], const uint32_t (&v)[EPT],
+                                              const bool (&ok)[EPT], const uint32_t (&gflag)[EPT], uint32_t gR,
+                                              FoldStats& st, uint32_t* marks_out = nullptr) {
+    uint32_t pu[EPT], pv[EPT], cx[EPT];
+    // one endpoint in the giant, the other x > gR: claim x straight under gR with a CAS from
+    // kInvalid instead of gathering parent[x] first. Success = x was never touched, and hanging a
+    // fresh singleton below any giant member (gR < x keeps parent[x] < x) is its union with the
+    // giant; failure returns parent[x], the word the gather would have read.
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
         const bool cu = ok[k] && gflag[k] == 2u && u[k] > gR;      // v in the giant, u outside
         const bool cv = ok[k] && gflag[k] == 1u && v[k] > gR;      // u in the giant, v outside
         pu[k] = !ok[k] ? 0u : (gflag[k] & 1u) ? gR : cu ? atomicCAS(&f.parent[u[k]], kInvalid, gR) : f.parent[u[k]];
         pv[k] = !ok[k] ? 0u : (gflag[k] & 2u) ? gR : cv ? atomicCAS(&f.parent[v[k]], kInvalid, gR) : f.parent[v[k]];
-        claimed[k] = (cu && pu[k] == kInvalid) || (cv && pv[k] == kInvalid);
+        const bool claimed = (cu && pu[k] == kInvalid) || (cv && pv[k] == kInvalid);
+        cx[k] = claimed ? (cu ? u[k] : v[k]) : kInvalid;
     }
-    uint32_t m[EPT];
 #pragma unroll
     for (int k = 0; k < EPT; ++k) {
-        if (claimed[k]) {
-            const uint32_t x = (gflag[k] == 2u) ? u[k] : v[k];
-            set_seen(f.sbits, x);                    // (a first touch: the seen bit, and the log)
-            if (STATS) { ++st.inits; ++st.hooks; }
-        }
+        if (cx[k] == kInvalid) continue;
+        // a claimed vertex is a depth-1 child of gR, the root the next incremental close labels
+        // the giant with: that close only sets its gbits bit (cbits, no parent[] read); a close
+        // that is a full pass reads every parent[] word anyway. Without cbits: the seen bit.
+        if (RING && f.cbits) set_mark(f.cbits, cx[k]);
+        else set_seen(f.sbits, cx[k]);
+        if (STATS) { ++st.inits; ++st.hooks; }
     }
-    if (f.tlog) {
-        NewV nl[EPT];
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            if (claimed[k]) {
-                nl[k].a = (gflag[k] == 2u) ? u[k] : v[k];
-                m[k] = MARK ? nl[k].a : kInvalid;
-            } else {
-                m[k] = ok[k] ? union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st, f.halve != 0,
-                                                       f.hbits, &nl[k]) : kInvalid;
-            }
-        }
-        uint32_t t[2 * EPT];
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            t[2 * k] = nl[k].a;
-            t[2 * k + 1] = nl[k].b;
-        }
-        slot_append<2 * EPT>(f.tlog, f.tcnt, t);
-    } else if (f.combine) {                          // pair folds: combined hooks (combine_hooks)
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            uint32_t cu = u[k], cv = v[k];
-            bool skip;
-            combine_hooks(f.parent, f.halve != 0, ok[k] && !claimed[k], cu, cv, pu[k], pv[k], skip);
-            if (claimed[k]) m[k] = MARK ? ((gflag[k] == 2u) ? u[k] : v[k]) : kInvalid;
-            else m[k] = (ok[k] && !skip) ? union_edge<MARK, STATS>(f.parent, f.sbits, cu, cv, pu[k], pv[k], &st, f.halve != 0, f.hbits)
-                                         : kInvalid;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            if (claimed[k]) m[k] = MARK ? ((gflag[k] == 2u) ? u[k] : v[k]) : kInvalid;
-            else m[k] = ok[k] ? union_edge<MARK, STATS>(f.parent, f.sbits, u[k], v[k], pu[k], pv[k], &st, f.halve != 0, f.hbits)
-                              : kInvalid;
-        }
-    }
-    if (MARK) log_append<EPT>(f.mark, f.mark_len, m);
+    union_tail<MARK, STATS, EPT, RING>(f, u, v, ok, pu, pv, cx, false, st, marks_out);
 }
 
 // Filter, parent gathers and unions of one thread's EPT edges (ids already range-checked;
@@ -859,7 +817,7 @@ __device__ __forceinline__ void fold_group(const FoldArgs& f, bool filt, uint32_
     if (STATS) for (int k = 0; k < EPT; ++k) nvalid += ok[k];
     uint32_t gflag[EPT];
     if (filt) filter_group<STATS, EPT, false>(f, u, v, ok, nullptr, HotArgs{nullptr, 0, nullptr}, false, false, ~0ull, gflag);
-    if (EPT == 1 && filt && claim_gR != kInvalid) union_group_gl<MARK, STATS, EPT>(f, u, v, ok, gflag, claim_gR, st);
+    if (EPT == 1 && filt && claim_gR != kInvalid) union_group_g<MARK, STATS, EPT, false>(f, u, v, ok, gflag, claim_gR, st);
     else union_group<MARK, STATS, EPT>(f, u, v, ok, st);
     if (STATS) {
         for (int k = 0; k < EPT; ++k) nfilt += ok[k];
@@ -964,12 +922,7 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold(const IdT* __restrict__ a
             fold_edges_at<IdT, AOS, MARK, VEC, EPT, STATS>(a, b, f, filt, g, st, claim_gR);
     }
     if (f.tlog && (threadIdx.x & 63) == 0) f.tlog[0] = s_tcnt[wave];   // every slot's count, 0 included
-    if (STATS) {
-        atomicAdd(&f.stats[2], (unsigned long long)st.early);
-        atomicAdd(&f.stats[3], (unsigned long long)st.hooks);
-        atomicAdd(&f.stats[4], (unsigned long long)st.casfail);
-        atomicAdd(&f.stats[5], (unsigned long long)st.inits);
-    }
+    if (STATS) st.flush(f.stats);
 }
 
 // Steady-state UpdateCC (mature forest, aligned uint32 SoA device edges): one 1024-thread
@@ -983,24 +936,26 @@ __global__ __launch_bounds__(kFoldThreads) void k_fold(const IdT* __restrict__ a
 constexpr int kRingCap = 128;                       // pairs per wave: 16 waves x 1 KiB of LDS
 // Ring entries carry the survivor's giant flags in bit 31 of each id (ids < 2^31 when gR != kInvalid,
 // see k_fold_ring).
+// The unions of the top min(n, 64) ring entries, one per lane; cnt drops by as many.
+template <bool MARK, bool STATS>
+__device__ __forceinline__ void ring_take(const FoldArgs& f, const uint2* ring, uint32_t& cnt, uint32_t n, FoldStats& st,
+                                          uint32_t gR, uint32_t* marks_out = nullptr) {
+    const uint32_t lane = threadIdx.x & 63, take = min(n, 64u);
+    cnt -= take;
+    const bool ok[1] = {lane < take};
+    const uint2 e = ok[0] ? ring[cnt + lane] : make_uint2(0u, 0u);
+    const uint32_t u[1] = {e.x & 0x7FFFFFFFu}, v[1] = {e.y & 0x7FFFFFFFu};
+    const uint32_t gf[1] = {(e.x >> 31) | ((e.y >> 31) << 1)};
+    union_group_g<MARK, STATS, 1, true>(f, u, v, ok, gf, gR, st, marks_out);
+}
+
 template <bool MARK, bool STATS>
 __device__ __forceinline__ void ring_flush(const FoldArgs& f, uint2* ring, uint32_t& cnt, uint32_t keep, FoldStats& st,
                                            uint32_t gR) {
-    const int lane = threadIdx.x & 63;
     // the ring is written and read by different lanes of this wave: order those LDS accesses
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    while (cnt > keep) {                            // uniform
-        const uint32_t take = min(cnt - keep, 64u);
-        const uint32_t at = cnt - take;
-        const bool ok1 = (uint32_t)lane < take;
-        const uint2 e = ok1 ? ring[at + lane] : make_uint2(0u, 0u);
-        const uint32_t u[1] = {e.x & 0x7FFFFFFFu}, v[1] = {e.y & 0x7FFFFFFFu};
-        const uint32_t gf[1] = {(e.x >> 31) | ((e.y >> 31) << 1)};
-        const bool ok[1] = {ok1};
-        union_group_g<MARK, STATS, 1>(f, u, v, ok, gf, gR, st);
-        cnt = at;
-    }
+    while (cnt > keep) ring_take<MARK, STATS>(f, ring, cnt, cnt - keep, st, gR);   // uniform
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
@@ -1022,18 +977,7 @@ __device__ __forceinline__ void ring_flush_final(const FoldArgs& f, uint2* ring,
     __builtin_amdgcn_wave_barrier();
     uint32_t mk[2] = {kInvalid, kInvalid};           // the ring holds at most 2 x 64 entries here
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        if (cnt == 0) break;                         // uniform
-        const uint32_t take = min(cnt, 64u);
-        const uint32_t at = cnt - take;
-        const bool ok1 = (uint32_t)lane < take;
-        const uint2 e = ok1 ? ring[at + lane] : make_uint2(0u, 0u);
-        const uint32_t u[1] = {e.x & 0x7FFFFFFFu}, v[1] = {e.y & 0x7FFFFFFFu};
-        const uint32_t gf[1] = {(e.x >> 31) | ((e.y >> 31) << 1)};
-        const bool ok[1] = {ok1};
-        union_group_g<MARK, STATS, 1>(f, u, v, ok, gf, gR, st, &mk[it]);
-        cnt = at;
-    }
+    for (int it = 0; it < 2 && cnt; ++it) ring_take<MARK, STATS>(f, ring, cnt, cnt, st, gR, &mk[it]);   // uniform
     __syncthreads();                                 // s_cnt is zeroed
     const uint64_t lt = (1ull << lane) - 1;
     const uint64_t b0 = __ballot(mk[0] != kInvalid), b1 = __ballot(mk[1] != kInvalid);
@@ -1051,12 +995,10 @@ __device__ __forceinline__ void ring_flush_final(const FoldArgs& f, uint2* ring,
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-// 16-B copy of WORDS 32-bit words global -> LDS by a 1024-thread workgroup, 8 loads in flight per
-// thread before any store: the element loop it replaces (load, wait, store) waited one round trip
-// per step, 16 of them to fill the hot set at every ring launch
+// 16-B copy of WORDS 32-bit words global -> LDS by the whole workgroup (THREADS threads), 8 loads in
+// flight per thread before any store: the element loop it replaces (load, wait, store) waited one
+// round trip per step, 16 of them to fill the hot set at every ring launch. Zero past `avail`.
 constexpr uint32_t kFillThreads = 1024;
-// 16-B copy of `words` 32-bit words global -> LDS by the whole workgroup, 8 loads in flight per
-// thread before any store (a load-store loop waits one round trip per step); zero past `avail`
 template <uint32_t WORDS, uint32_t THREADS = kFillThreads>
 __device__ __forceinline__ void lds_fill(uint32_t* __restrict__ dst, const uint32_t* __restrict__ src, uint64_t avail) {
     constexpr uint32_t kVecs = WORDS / 4;
@@ -1080,8 +1022,6 @@ __device__ __forceinline__ void lds_fill(uint32_t* __restrict__ dst, const uint3
         }
     }
 }
-
-
 
 // 4 consecutive ids of an aligned SoA stream, loaded raw (load) and range-checked as uint32 where
 // they are used (unpack): int64 ids take two 16-B loads; a negative or >= cap id fails the range
@@ -1115,6 +1055,67 @@ struct Raw4<int64_t> {
     }
 };
 
+// The whole group g (4 edges) of two 16-B aligned streams: ok[k] = both ids in range; an id out of
+// range raises rc.err and its edge is zeroed (the filter may index with it).
+template <typename IdT>
+__device__ __forceinline__ void load_group4(const IdT* __restrict__ a, const IdT* __restrict__ b, uint64_t g,
+                                            const RangeCheck& rc, uint32_t (&u)[4], uint32_t (&v)[4], bool (&ok)[4]) {
+    bool oka[4] = {true, true, true, true}, okb[4] = {true, true, true, true};
+    Raw4<IdT> ra, rb;
+    ra.load(a, g);
+    rb.load(b, g);
+    ra.unpack(u, oka, rc.cap);
+    rb.unpack(v, okb, rc.cap);
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        ok[k] = oka[k] && okb[k];
+        bad |= !ok[k];
+        if (!ok[k]) { u[k] = 0; v[k] = 0; }
+    }
+    if (bad) atomicOr(rc.err, 1u);
+}
+
+// inclusive prefix sum of c over the wave's 64 lanes (all active)
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t c) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(c, off, 64);
+        if (lane >= off) c += y;
+    }
+    return c;
+}
+
+// What a steady launch (k_fold_ring, k_filter_out) derives from HotArgs at its head. !HOT: the
+// launch has no hot / warm set (the host passes HotArgs{}): everything off, no HotArgs pointer read.
+struct HotLaunch {
+    uint32_t budget = 0;         // admitting launches left, as read at entry (no budget word: no cadence, 1)
+    uint64_t sample_edges = 0;   // admission offers the endpoints of this launch's first edges
+    uint64_t count_edges = 0;    // warm build: count this launch's first edges
+    bool warm_ok = false;        // probe the warm set
+    // All uniform. Admitting launch? (read before workgroup 0's decrement may land: a workgroup that reads the
+    // decremented budget only skips this launch's admission, which is a heuristic anyway)
+    template <bool HOT>
+    __device__ __forceinline__ static HotLaunch read(const HotArgs& hot, bool filt) {
+        HotLaunch s;
+        if (!HOT) return s;
+        s.budget = hot.budget ? *hot.budget : 1u;
+        s.sample_edges = (hot.periodic || s.budget) ? hot.sample_edges : 0;
+        s.warm_ok = filt && hot.warm && *hot.warm_valid != 0;
+        s.count_edges = (filt && hot.wkeys && hot.warm_valid && *hot.warm_valid == 0) ? hot.count_edges : 0;
+        return s;
+    }
+    // workgroup 0, after the barrier that follows read(): one admitting launch less, and the edges
+    // whose key slots this launch writes (filter_group's count_slot) for the warm build
+    template <bool HOT>
+    __device__ __forceinline__ void commit(const HotArgs& hot, uint64_t n) const {
+        if (!HOT || blockIdx.x != 0 || threadIdx.x != 0) return;
+        if (hot.budget && budget) *hot.budget = budget - 1;
+        if (hot.wkeys) *hot.wctl = (min(count_edges, n / 4 * 4) + 255) / 256 * 256;
+    }
+};
+
 // GSGPU_RING_CLOCKS only (the CLK instance of k_fold_ring; production launches the one without):
 // per-workgroup clocks (wall_clock64) of the last k_fold_ring launch — entry, hot set in LDS, every
 // wave's main loop done, final flush done (report_ring_clocks prints them)
@@ -1137,17 +1138,10 @@ __global__ __launch_bounds__(kHotThreads) void k_fold_ring(const IdT* __restrict
     // flags use it in place of a parent[] read (union_group_g). Off (kInvalid) without a filter
     // or for ids >= 2^31 (the ring's flag bit)
     const uint32_t gR = (filt && f.rc.cap <= 0x80000000u) ? f.giant[1] : kInvalid;
-    // admitting launch? (read before workgroup 0's decrement may land: a workgroup that reads the
-    // decremented budget only skips this launch's admission, which is a heuristic anyway)
-    const uint32_t budget = hot.budget ? *hot.budget : 1u;
-    const uint64_t sample_edges = (hot.periodic || budget) ? hot.sample_edges : 0;
-    const bool warm_ok = filt && hot.warm && *hot.warm_valid != 0;                        // uniform
-    const uint64_t count_edges = (filt && hot.wkeys && hot.warm_valid && *hot.warm_valid == 0) ? hot.count_edges : 0;
+    const HotLaunch hl = HotLaunch::read<true>(hot, filt);
     __syncthreads();
     if (clocks) g_ring_phase[blockIdx.x][1] = wall_clock64();
-    if (blockIdx.x == 0 && threadIdx.x == 0 && hot.budget && budget) *hot.budget = budget - 1;
-    if (blockIdx.x == 0 && threadIdx.x == 0 && hot.wkeys)            // key slots written below
-        *hot.wctl = (min(count_edges, n / 4 * 4) + 255) / 256 * 256;
+    hl.commit<true>(hot, n);
     const int lane = threadIdx.x & 63;
     uint2* const ring = rings[threadIdx.x >> 6];
     uint32_t cnt = 0;                                // wave-uniform ring fill
@@ -1161,41 +1155,21 @@ __global__ __launch_bounds__(kHotThreads) void k_fold_ring(const IdT* __restrict
         uint32_t u[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
         bool ok[4] = {false, false, false, false};
         uint32_t gf[4] = {0u, 0u, 0u, 0u};
-        if (g < groups) {
-            bool oka[4] = {true, true, true, true}, okb[4] = {true, true, true, true};
-            Raw4<IdT> ra, rb;
-            ra.load(a, g);
-            rb.load(b, g);
-            ra.unpack(u, oka, f.rc.cap);
-            rb.unpack(v, okb, f.rc.cap);
-            bool bad = false;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                ok[k] = oka[k] && okb[k];
-                bad |= !ok[k];
-                if (!ok[k]) { u[k] = 0; v[k] = 0; }
-            }
-            if (bad) atomicOr(f.rc.err, 1u);
-        }
+        if (g < groups) load_group4<IdT>(a, b, g, f.rc, u, v, ok);
         if (STATS) for (int k = 0; k < 4; ++k) nvalid += ok[k];
-        if (filt) filter_group<STATS, 4, true>(f, u, v, ok, tab, hot, g * 4 < sample_edges, warm_ok,
-                                               g0 * 4 < count_edges ? g0 / 64 : ~0ull, gf);
+        if (filt) filter_group<STATS, 4, true>(f, u, v, ok, tab, hot, g * 4 < hl.sample_edges, hl.warm_ok,
+                                               g0 * 4 < hl.count_edges ? g0 / 64 : ~0ull, gf);
         if (gR == kInvalid) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) gf[k] = 0u;
         }
         const uint32_t c = (uint32_t)ok[0] + ok[1] + ok[2] + ok[3];
         if (STATS) nkept += c;
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
+        const uint32_t incl = wave_inclusive_scan(c);
         const uint32_t wtot = __shfl(incl, 63, 64);
         if (wtot == 0) return;                       // uniform
         if (wtot > kRingCap / 2) {                   // young window: union in place
-            union_group_g<MARK, STATS, 4>(f, u, v, ok, gf, gR, st);
+            union_group_g<MARK, STATS, 4, true>(f, u, v, ok, gf, gR, st);
             return;
         }
         if (cnt + wtot > kRingCap) ring_flush<MARK, STATS>(f, ring, cnt, kRingCap - wtot, st, gR);
@@ -1225,10 +1199,7 @@ __global__ __launch_bounds__(kHotThreads) void k_fold_ring(const IdT* __restrict
     if (STATS) {
         atomicAdd(&f.stats[0], nvalid);
         atomicAdd(&f.stats[1], nvalid - nkept);
-        atomicAdd(&f.stats[2], (unsigned long long)st.early);
-        atomicAdd(&f.stats[3], (unsigned long long)st.hooks);
-        atomicAdd(&f.stats[4], (unsigned long long)st.casfail);
-        atomicAdd(&f.stats[5], (unsigned long long)st.inits);
+        st.flush(f.stats);
     }
 }
 
@@ -1254,15 +1225,10 @@ __global__ __launch_bounds__(kHotThreads) void k_filter_out(const IdT* __restric
     const uint64_t n = f.n;
     const bool filt = *f.giant != kInvalid;          // uniform: a bitmap has been broadcast
     if (HOT && filt) lds_fill<2 * kHotBuckets>(reinterpret_cast<uint32_t*>(tab), reinterpret_cast<const uint32_t*>(hot.table), 2 * kHotBuckets);
-    const uint32_t budget = (HOT && hot.budget) ? *hot.budget : 0u;
-    const uint64_t sample_edges = (HOT && (hot.periodic || budget)) ? hot.sample_edges : 0;
-    const bool warm_ok = HOT && filt && hot.warm && *hot.warm_valid != 0;
-    const uint64_t count_edges = (HOT && filt && hot.wkeys && hot.warm_valid && *hot.warm_valid == 0) ? hot.count_edges : 0;
+    const HotLaunch hl = HotLaunch::read<HOT>(hot, filt);
     if (threadIdx.x == 0) s_pos = 0;
     __syncthreads();
-    if (HOT && blockIdx.x == 0 && threadIdx.x == 0 && hot.budget && budget) *hot.budget = budget - 1;
-    if (HOT && blockIdx.x == 0 && threadIdx.x == 0 && hot.wkeys)
-        *hot.wctl = (min(count_edges, n / 4 * 4) + 255) / 256 * 256;
+    hl.commit<HOT>(hot, n);
     const int lane = threadIdx.x & 63;
     uint2* const reg = regions + (uint64_t)blockIdx.x * region;
     const uint64_t groups = (n + 3) / 4;             // a partial last group: its lanes past n are not ok
@@ -1274,45 +1240,26 @@ __global__ __launch_bounds__(kHotThreads) void k_filter_out(const IdT* __restric
         uint32_t u[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
         bool ok[4] = {false, false, false, false};
         uint32_t gf[4];
-        if (g < groups) {
-            bool oka[4] = {true, true, true, true}, okb[4] = {true, true, true, true};
-            if (aligned && (vec || g + 1 < groups)) {
-                Raw4<IdT> ra, rb;
-                ra.load(a, g);
-                rb.load(b, g);
-                ra.unpack(u, oka, f.rc.cap);
-                rb.unpack(v, okb, f.rc.cap);
-            } else {                                 // unaligned, or the ragged last group
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const uint64_t e = 4 * g + k;
-                    const bool in = e < n;
-                    const uint64_t x = in ? (uint64_t)a[e] : 0, y = in ? (uint64_t)b[e] : 0;
-                    oka[k] = x < (uint64_t)f.rc.cap || !in;
-                    okb[k] = y < (uint64_t)f.rc.cap || !in;
-                    u[k] = (uint32_t)x;
-                    v[k] = (uint32_t)y;
-                }
-            }
+        if (g < groups && aligned && (vec || g + 1 < groups)) {
+            load_group4<IdT>(a, b, g, f.rc, u, v, ok);
+        } else if (g < groups) {                     // unaligned, or the ragged last group: by element
             bool bad = false;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const bool in = 4 * g + k < n;
-                ok[k] = in && oka[k] && okb[k];
-                bad |= in && !(oka[k] && okb[k]);
-                if (!ok[k]) { u[k] = 0; v[k] = 0; }
+                const uint64_t e = 4 * g + k;
+                const bool in = e < n;
+                const uint64_t x = in ? (uint64_t)a[e] : 0, y = in ? (uint64_t)b[e] : 0;
+                ok[k] = in && x < (uint64_t)f.rc.cap && y < (uint64_t)f.rc.cap;
+                bad |= in && !ok[k];
+                u[k] = ok[k] ? (uint32_t)x : 0u;
+                v[k] = ok[k] ? (uint32_t)y : 0u;
             }
             if (bad) atomicOr(f.rc.err, 1u);
         }
-        if (filt) filter_group<false, 4, HOT>(f, u, v, ok, tab, hot, g * 4 < sample_edges, warm_ok,
-                                              g0 * 4 < count_edges ? g0 / 64 : ~0ull, gf);
+        if (filt) filter_group<false, 4, HOT>(f, u, v, ok, tab, hot, g * 4 < hl.sample_edges, hl.warm_ok,
+                                              g0 * 4 < hl.count_edges ? g0 / 64 : ~0ull, gf);
         const uint32_t c = (uint32_t)ok[0] + ok[1] + ok[2] + ok[3];
-        uint32_t incl = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
+        const uint32_t incl = wave_inclusive_scan(c);
         const uint32_t wtot = __shfl(incl, 63, 64);
         if (wtot == 0) continue;                     // uniform
         uint32_t base = 0;
