@@ -24,12 +24,13 @@
 // agree on it), a walk treats a word that is not below its index (a stale kInvalid) as a root.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <unordered_map>
 #include <vector>
 
 #include <hipcub/hipcub.hpp>
 
-#include "common.hpp"
+#include "owned.hpp"
 #include "bip_literal.hpp"
 
 namespace gsgpu {
@@ -356,24 +357,23 @@ using namespace gsgpu;
 
 // device state of a GS_BIP_REFERENCE_LITERAL summary (bip_literal.hpp), in one allocation
 struct LitDev {
-    void* mem = nullptr;
+    DevBuf<> mem;
     lit::State S{};
-    lit::Ctl* hctl = nullptr;                     // pinned mirror of S.ctl
+    Pinned<lit::Ctl> hctl;                        // pinned mirror of S.ctl
 };
 
 struct gs_bip {
     uint32_t cap = 0, id_bits = 64;
     int device = 0;
-    LitDev* lit = nullptr;                     // GS_BIP_REFERENCE_LITERAL: the literal engine's state
-    hipStream_t own = nullptr, stream = nullptr;
-    uint32_t* w = nullptr;
-    uint32_t* flags = nullptr;                 // [0] range error, [1] not bipartite
-    unsigned long long* dscr = nullptr;        // reductions
-    unsigned long long* hscr = nullptr;        // pinned mirror
-    void* tmp = nullptr;
-    size_t tmp_bytes = 0;
-    void* stage = nullptr;
-    size_t stage_bytes = 0;
+    Stream own;
+    hipStream_t stream = nullptr;              // own, or the caller's (gs_bip_set_stream)
+    std::unique_ptr<LitDev> lit;               // GS_BIP_REFERENCE_LITERAL: the literal engine's state
+    DevBuf<uint32_t> w;
+    DevBuf<uint32_t> flags;                    // [0] range error, [1] not bipartite
+    DevBuf<unsigned long long> dscr;           // reductions
+    Pinned<unsigned long long> hscr;           // pinned mirror
+    DevBuf<> tmp;
+    DevBuf<> stage;
     uint64_t edges_since_reset = 0;
     bool compressed = true;
 };
@@ -383,14 +383,6 @@ namespace {
 BipArgs bargs(gs_bip_t* h) { return BipArgs{h->w, h->cap, h->flags}; }
 
 int bcheck(gs_bip_t* h) { return h ? GS_OK : fail(GS_ERR_INVALID, "null handle"); }
-
-int bensure(void** p, size_t* have, size_t need) {
-    if (*have >= need) return GS_OK;
-    if (*p) { GS_HIP(hipFree(*p)); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, need) != hipSuccess) { (void)hipGetLastError(); return fail(GS_ERR_NOMEM, "hipMalloc(%zu) failed", need); }
-    *have = need;
-    return GS_OK;
-}
 
 // literal engine: its control words to the host, errors mapped to GS_ERR_* (the range flag is
 // cleared once reported, as the union-find's is)
@@ -486,10 +478,10 @@ int bfold(gs_bip_t* h, const void* a, const void* b, uint64_t n, bool aos) {
         return GS_OK;
     }
     const uint64_t chunk = 1ull << 22;
-    GS_TRY(bensure(&h->stage, &h->stage_bytes, chunk * esz * 2));
+    GS_TRY(h->stage.grow(chunk * esz * 2, "bipartite fold staging"));
     for (uint64_t off = 0; off < n; off += chunk) {
         const uint64_t m = std::min(n - off, chunk);
-        char* s0 = static_cast<char*>(h->stage);
+        char* s0 = static_cast<char*>(h->stage.get());
         char* s1 = s0 + chunk * esz;
         if (aos) {
             GS_HIP(hipMemcpyAsync(s0, static_cast<const char*>(a) + off * esz * 2, m * esz * 2, hipMemcpyHostToDevice, h->stream));
@@ -519,8 +511,8 @@ int lemit(gs_bip_t* h, void* vertices, void* keys, uint8_t* signs, uint64_t cap,
         const size_t kb = ((size_t)total * 8 + 255) & ~(size_t)255, sb = ((size_t)total + 255) & ~(size_t)255;
         const size_t esz = h->id_bits / 8;
         const size_t ob = ((size_t)wn * (2 * esz + 1) + 255) & ~(size_t)255;
-        GS_TRY(bensure(&h->tmp, &h->tmp_bytes, 256 + 2 * kb + 2 * sb + ob + sort_bytes));
-        char* base = static_cast<char*>(h->tmp);
+        GS_TRY(h->tmp.grow(256 + 2 * kb + 2 * sb + ob + sort_bytes, "bipartite temporaries"));
+        char* base = static_cast<char*>(h->tmp.get());
         auto* acc = reinterpret_cast<unsigned long long*>(base);
         auto* ki = reinterpret_cast<uint64_t*>(base + 256);
         auto* ko = reinterpret_cast<uint64_t*>(base + 256 + kb);
@@ -584,20 +576,18 @@ int gs_bip_create_ex(gs_bip_t** out, uint64_t vertex_capacity, uint32_t id_bits,
     h->cap = (uint32_t)vertex_capacity;
     h->id_bits = id_bits;
     h->device = device;
-    auto bail = [&](int rc) { gs_bip_destroy(h); return rc; };
-    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess) return bail(fail(GS_ERR_HIP, "hipStreamCreate failed"));
+    struct Destroy { void operator()(gs_bip_t* p) const { (void)gs_bip_destroy(p); } };
+    std::unique_ptr<gs_bip_t, Destroy> guard(h);      // a failure below destroys what exists so far
+    GS_TRY(h->own.create());
     h->stream = h->own;
-    if (hipMalloc(&h->dscr, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(&h->hscr, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(GS_ERR_NOMEM, "gs_bip_create: scratch allocation failed"));
-    }
+    GS_TRY(h->dscr.grow(8, "gs_bip_create: scratch"));
+    GS_TRY(h->hscr.alloc(8, "gs_bip_create: scratch"));
     if (flags & GS_BIP_REFERENCE_LITERAL) {
         // the literal engine: nodes E (component memberships ever made between resets), as many
         // component slots, an arena of 4 E member slots (component arrays double as they grow)
         const uint64_t E = entry_capacity ? entry_capacity : std::max<uint64_t>(16ull * h->cap, 4096);
-        if (E > 0x7FFFFFFFull / 4) return bail(fail(GS_ERR_INVALID, "gs_bip_create_ex: entry_capacity too large"));
-        h->lit = new LitDev();
+        if (E > 0x7FFFFFFFull / 4) return fail(GS_ERR_INVALID, "gs_bip_create_ex: entry_capacity too large");
+        h->lit.reset(new LitDev());
         lit::State& S = h->lit->S;
         S.cap = h->cap;
         S.E = (uint32_t)E;
@@ -611,12 +601,9 @@ int gs_bip_create_ex(gs_bip_t** out, uint64_t vertex_capacity, uint32_t id_bits,
                      o_ck = take(E * 4), o_ca = take(E * 4), o_cb = take(E * 4), o_csz = take(E * 4), o_ccap = take(E * 4),
                      o_cnt = take(E * 4), o_tch = take(E * 4), o_mw = take(E * 8), o_mws = take(E * 8),
                      o_arena = take(4 * E * 4), o_ctl = take(sizeof(lit::Ctl));
-        if (hipMalloc(&h->lit->mem, off) != hipSuccess ||
-            hipHostMalloc(&h->lit->hctl, sizeof(lit::Ctl), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return bail(fail(GS_ERR_NOMEM, "gs_bip_create_ex: %zu bytes for the reference-literal summary", off));
-        }
-        char* m = static_cast<char*>(h->lit->mem);
+        GS_TRY(h->lit->mem.grow(off, "gs_bip_create_ex: the reference-literal summary"));
+        GS_TRY(h->lit->hctl.alloc(1, "gs_bip_create_ex: the reference-literal summary"));
+        char* m = static_cast<char*>(h->lit->mem.get());
         S.vhead = (int32_t*)(m + o_vhead);
         S.kslot = (int32_t*)(m + o_kslot);
         S.sv = (uint32_t*)(m + o_sv);
@@ -636,14 +623,13 @@ int gs_bip_create_ex(gs_bip_t** out, uint64_t vertex_capacity, uint32_t id_bits,
         S.mws = (uint64_t*)(m + o_mws);
         S.arena = (int32_t*)(m + o_arena);
         S.ctl = (lit::Ctl*)(m + o_ctl);
-    } else if (hipMalloc(&h->w, (size_t)h->cap * 4) != hipSuccess || hipMalloc(&h->flags, 16) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(GS_ERR_NOMEM, "gs_bip_create: allocation of %u words failed", h->cap));
+    } else {
+        GS_TRY(h->w.grow(h->cap, "gs_bip_create: summary"));
+        GS_TRY(h->flags.grow(4, "gs_bip_create: summary"));
     }
-    int rc = gs_bip_reset(h);
-    if (rc != GS_OK) return bail(rc);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(GS_ERR_HIP, "stream sync failed"));
-    *out = h;
+    GS_TRY(gs_bip_reset(h));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    *out = guard.release();
     return GS_OK;
 }
 
@@ -651,17 +637,8 @@ int gs_bip_destroy(gs_bip_t* h) {
     if (!h) return GS_OK;
     DeviceGuard g(h->device);
     if (h->own) (void)hipStreamSynchronize(h->own);
-    if (h->stream && h->stream != h->own) (void)hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->w, (void*)h->flags, (void*)h->dscr, h->tmp, h->stage})
-        if (p) (void)hipFree(p);
-    if (h->hscr) (void)hipHostFree(h->hscr);
-    if (h->lit) {
-        if (h->lit->mem) (void)hipFree(h->lit->mem);
-        if (h->lit->hctl) (void)hipHostFree(h->lit->hctl);
-        delete h->lit;
-    }
-    if (h->own) (void)hipStreamDestroy(h->own);
-    delete h;
+    if (h->stream && h->stream != h->own.get()) (void)hipStreamSynchronize(h->stream);
+    delete h;                                  // the owners free what it holds (owned.hpp)
     return GS_OK;
 }
 
@@ -706,9 +683,9 @@ int gs_bip_merge(gs_bip_t* into, gs_bip_t* from) {
     if ((into->lit == nullptr) != (from->lit == nullptr))
         return fail(GS_ERR_UNSUPPORTED, "gs_bip_merge: a reference-literal and an intended-semantics summary do not mix");
     DeviceGuard g(into->device);
-    hipEvent_t e = nullptr;
+    Event e;
     if (from->stream != into->stream) {
-        GS_HIP(hipEventCreate(&e));
+        GS_TRY(e.create());
         GS_HIP(hipEventRecord(e, from->stream));
         GS_HIP(hipStreamWaitEvent(into->stream, e, 0));
     }
@@ -722,7 +699,6 @@ int gs_bip_merge(gs_bip_t* into, gs_bip_t* from) {
     if (e) {
         GS_HIP(hipEventRecord(e, into->stream));
         GS_HIP(hipStreamWaitEvent(from->stream, e, 0));
-        GS_HIP(hipEventDestroy(e));
     }
     return GS_OK;
 }
@@ -788,9 +764,9 @@ int gs_bip_emit_pairs(gs_bip_t* h, void* vertices, void* keys, uint8_t* signs, u
     const uint32_t nt = (uint32_t)((h->cap + kBipTile - 1) / kBipTile);
     const size_t esz = h->id_bits / 8;
     const size_t cnt_b = ((size_t)nt * 4 + 255) & ~(size_t)255, off_b = ((size_t)(nt + 1) * 8 + 255) & ~(size_t)255;
-    GS_TRY(bensure(&h->tmp, &h->tmp_bytes, cnt_b + off_b));
-    uint32_t* cnt = static_cast<uint32_t*>(h->tmp);
-    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp) + cnt_b);
+    GS_TRY(h->tmp.grow(cnt_b + off_b, "bipartite temporaries"));
+    uint32_t* cnt = static_cast<uint32_t*>(h->tmp.get());
+    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp.get()) + cnt_b);
     hipLaunchKernelGGL(k_bip_count, dim3(nt), dim3(256), 0, h->stream, (const uint32_t*)h->w, h->cap, cnt);
     hipLaunchKernelGGL(k_bip_scan, dim3(1), dim3(1024), 0, h->stream, (const uint32_t*)cnt, off, nt);
     GS_HIP(hipGetLastError());
@@ -805,12 +781,12 @@ int gs_bip_emit_pairs(gs_bip_t* h, void* vertices, void* keys, uint8_t* signs, u
         void* ko = keys;
         uint8_t* so = signs;
         if (!dev) {
-            GS_TRY(bensure(&h->tmp, &h->tmp_bytes, cnt_b + off_b + wn * (2 * esz + 1)));
-            off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp) + cnt_b);
-            cnt = static_cast<uint32_t*>(h->tmp);
+            GS_TRY(h->tmp.grow(cnt_b + off_b + wn * (2 * esz + 1), "bipartite temporaries"));
+            off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp.get()) + cnt_b);
+            cnt = static_cast<uint32_t*>(h->tmp.get());
             hipLaunchKernelGGL(k_bip_count, dim3(nt), dim3(256), 0, h->stream, (const uint32_t*)h->w, h->cap, cnt);
             hipLaunchKernelGGL(k_bip_scan, dim3(1), dim3(1024), 0, h->stream, (const uint32_t*)cnt, off, nt);
-            vo = static_cast<char*>(h->tmp) + cnt_b + off_b;
+            vo = static_cast<char*>(h->tmp.get()) + cnt_b + off_b;
             ko = static_cast<char*>(vo) + wn * esz;
             so = static_cast<uint8_t*>(ko) + wn * esz;
         }
@@ -905,8 +881,8 @@ int gs_bip_restore(gs_bip_t* h, int bipartite, const void* vertices, const void*
                         "(gs_bip_create_ex entry_capacity)", (unsigned long long)n, rk.size(), S.E, S.C);
         const size_t b_rk = (rk.size() * 4 + 255) & ~(size_t)255, b_ro = (ro.size() * 8 + 255) & ~(size_t)255,
                      b_rv = ((size_t)n * 4 + 255) & ~(size_t)255;
-        GS_TRY(bensure(&h->tmp, &h->tmp_bytes, b_rk + b_ro + b_rv + n));
-        char* base = static_cast<char*>(h->tmp);
+        GS_TRY(h->tmp.grow(b_rk + b_ro + b_rv + n, "bipartite temporaries"));
+        char* base = static_cast<char*>(h->tmp.get());
         GS_HIP(hipMemcpy(base, rk.data(), rk.size() * 4, hipMemcpyHostToDevice));
         GS_HIP(hipMemcpy(base + b_rk, ro.data(), ro.size() * 8, hipMemcpyHostToDevice));
         GS_HIP(hipMemcpy(base + b_rk + b_ro, rv.data(), (size_t)n * 4, hipMemcpyHostToDevice));

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <type_traits>
 #include <mutex>
 #include <vector>
@@ -12,26 +13,12 @@
 
 #include "cc_internal.hpp"
 #include "cc_kernels.hpp"
+#include "owned.hpp"
 #include "sparse_ids.hpp"
 
 #include <hipcub/hipcub.hpp>
 
 namespace gsgpu {
-
-std::string& last_error() {
-    static thread_local std::string s;
-    return s;
-}
-
-int fail(int code, const char* fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    last_error() = buf;
-    return code;
-}
 
 bool is_device_pointer(const void* p) {
     if (!p) return false;
@@ -59,50 +46,66 @@ struct gs_cc {
     gs_cc_config cfg{};
     uint32_t cap = 0;
     int device = 0;
-    hipStream_t own = nullptr, stream = nullptr;
-    uint32_t* parent = nullptr;          // dense summary / label array
+    Stream own;
+    hipStream_t stream = nullptr;        // own, or the caller's (gs_cc_set_stream)
+    DevBuf<uint32_t> parent;             // dense summary / label array
     uint32_t* mark = nullptr;            // hook log while marking (GS_CC_TRACK_MARKS), else null
-    uint32_t* mark_buf = nullptr;        // the hook log: 2 x capacity entries (cc_kernels.hpp log_append)
-    unsigned long long* mark_ctr = nullptr;   // [log length, export cursor], a 128-B line of its own
-    uint32_t* gbits = nullptr;           // giant-component filter bitmap (1 bit per vertex)
-    uint32_t* sbits = nullptr;           // seen bitmap (1 bit per vertex), set on first touch
-    uint32_t* cbits = nullptr;           // ring folds: first touches claimed under the giant root
-    uint32_t* hkbits[2] = {nullptr, nullptr}; // roots hooked before any giant exists, by close parity
+    DevBuf<uint32_t> mark_buf;           // the hook log: 2 x capacity entries (cc_kernels.hpp log_append)
+    DevBuf<unsigned long long> mark_ctr; // kMarkCtrWords: [log length, export cursor, exporting workgroups done], a 128-B line of its own
+    DevBuf<uint32_t> gbits;              // giant-component filter bitmap (1 bit per vertex)
+    DevBuf<uint32_t> sbits;              // seen bitmap (1 bit per vertex), set on first touch
+    DevBuf<uint32_t> cbits;              // ring folds: first touches claimed under the giant root
+    DevBuf<uint32_t> hkbits[2];          // roots hooked before any giant exists, by close parity
     bool hkbits_ok = true;               // every fold since the last close marked its hooked roots
-    uint32_t* dbits = nullptr;           // delta emission: vertices a close may have relabelled since the last delta
+    DevBuf<uint32_t> dbits;              // delta emission: vertices a close may have relabelled since the last delta
     // list-mode closes (cc_kernels.hpp ListCtl): control words, the NGL (seen vertices outside the
     // giant) and the touch log, each double-buffered by close parity
-    uint32_t* lctl = nullptr;
-    uint2* ngl[2] = {nullptr, nullptr};
-    uint32_t* tlog[2] = {nullptr, nullptr};
+    DevBuf<uint32_t> lctl;
+    DevBuf<uint2> ngl[2];
+    DevBuf<uint32_t> tlog[2];
     uint32_t ngl_sub = 0;
     bool ilist_ok = true;                // every fold since the last close logged its first touches
     uint32_t ilist_folds = 0;            // logged folds since the last close
     uint32_t ilist_slots = 0;            // touch-log slots they took (one per wave)
     bool list_prev = false;              // the last close built an NGL (list_next)
     bool list_kernel = false;            // the last close ran k_compress_list (its control words are current)
-    uint32_t* elab = nullptr;            // delta emission: the labels last emitted (kInvalid: never)
-    uint32_t* derr = nullptr;            // derr[0] deferred device error flags; derr[1..5] giant state
-    uint32_t* psamp = nullptr;           // 2 x kPickSamples labels a full-pass close recorded (k_compress)
+    DevBuf<uint32_t> elab;               // delta emission: the labels last emitted (kInvalid: never)
+    DevBuf<uint32_t> derr;               // the control block (enum Ctl below)
+    DevBuf<uint32_t> psamp;              // 2 x kPickSamples labels a full-pass close recorded (k_compress)
     // a multi-GPU window whose exchange is still to be verified (comm.hip: the speculative
     // all-gather's delta sizes are checked lazily, so the host never waits for them per window):
     // every call that consumes the emission runs it first (cc_settle)
     int (*settle_fn)(void*) = nullptr;
     void* settle_ctx = nullptr;
-    unsigned long long* dscratch = nullptr;  // reduction outputs (8 words)
-    unsigned long long* hscratch = nullptr;  // pinned mirror
-    void* stage = nullptr;               // host->device staging: 2 slots x (src, dst) x staging_edges ids
-    size_t stage_bytes = 0;
-    hipStream_t copy = nullptr;          // H2D copies of host-buffer folds (double-buffered staging)
-    hipEvent_t staged[2] = {nullptr, nullptr}, freed[2] = {nullptr, nullptr};
-    void* tmp = nullptr;                 // emission temporaries
-    size_t tmp_bytes = 0;
+    DevBuf<unsigned long long> dscratch; // reduction outputs (8 words)
+    Pinned<unsigned long long> hscratch; // pinned mirror (8 words: kHostFilterCount, kHostErr, results from word 0)
+    DevBuf<> stage;                      // host->device staging: 2 slots x (src, dst) x staging_edges ids
+    // H2D copies of host-buffer folds (double-buffered staging), made on the first such fold
+    struct Staging {
+        Stream copy;
+        Event staged[2], freed[2];
+        int create() {
+            GS_TRY(copy.create());
+            for (int k = 0; k < 2; ++k) { GS_TRY(staged[k].create()); GS_TRY(freed[k].create()); }
+            return GS_OK;
+        }
+    } sg;
+    DevBuf<> tmp;                        // emission temporaries
     // delta emission (gs_cc_emit_delta[_async]): two slots of packed pairs; an async emission's
     // slot is copied out on estream (k_delta_copy: device / pinned buffers) or at gs_cc_emit_wait
-    struct EmitSlot { void* mem = nullptr; size_t bytes = 0; hipEvent_t staged = nullptr, done = nullptr; };
-    EmitSlot eslot[2];
-    unsigned long long* ecount = nullptr;    // pinned: the size of each slot's delta
-    hipStream_t estream = nullptr;
+    DevBuf<> eslot[2];
+    // ... and what an async emission needs besides, made on the first one
+    struct EmitAsync {
+        Stream estream;
+        Pinned<unsigned long long> ecount;   // the size of each slot's delta
+        Event staged[2], done[2];            // per slot
+        int create() {
+            GS_TRY(estream.create());
+            GS_TRY(ecount.alloc(2, "gs_cc_emit_delta_async"));
+            for (int k = 0; k < 2; ++k) { GS_TRY(staged[k].create()); GS_TRY(done[k].create()); }
+            return GS_OK;
+        }
+    } ea;
     struct EmitPend { int slot; uint64_t* n_out; uint64_t cap; void* vertices; void* labels; bool kcopy; };
     EmitPend epend[2];                   // async emissions not yet waited for, oldest first
     int n_epend = 0;
@@ -114,39 +117,37 @@ struct gs_cc {
     uint64_t closes = 0;                 // compressions since reset (giant re-sampled every kPickEvery)
     uint64_t pick_edges = 0;             // edges_since_reset at the last forced giant re-pick
     uint64_t reset_gen = 0;              // gs_cc_reset calls (a communicator's per-stream state follows it)
-    unsigned long long* dstats = nullptr;    // GSGPU_FOLD_STATS=1: per-window fold counters
+    DevBuf<unsigned long long> dstats;   // GSGPU_FOLD_STATS=1: per-window fold counters
     unsigned ring_clock_groups = 0;          // ... and the last k_fold_ring launch's clocks (its grid)
-    uint2* hot = nullptr;                // LDS hot set master copy (kHotBuckets uint2), steady folds
+    DevBuf<uint2> hot;                   // LDS hot set master copy (kHotBuckets uint2), steady folds
     uint32_t hot_bits = 0;               // ids < 2^hot_bits
-    uint32_t* hot_cand = nullptr;        // hot-set admission candidates (2^kHotCandBits ids)
-    uint32_t* warm = nullptr;            // warm set (2^warm_bits words, L2-resident), steady folds
+    DevBuf<uint32_t> hot_cand;           // hot-set admission candidates (2^kHotCandBits ids)
+    DevBuf<uint32_t> warm;               // warm set (2^warm_bits words, L2-resident), steady folds
     uint32_t warm_bits = 0;
-    uint32_t* wkeys = nullptr;           // warm build: sampled endpoint key slots
-    uint16_t* wpart = nullptr;           // warm build: keys by hash bucket
-    unsigned long long* wctl = nullptr;  // warm build: [0] edges counted, then bucket fills (u32)
+    DevBuf<uint32_t> wkeys;              // warm build: sampled endpoint key slots
+    DevBuf<uint16_t> wpart;              // warm build: keys by hash bucket
+    DevBuf<unsigned long long> wctl;     // warm build: [0] edges counted, then bucket fills (u32)
     uint64_t warm_sample = 0;            // edges a warm count launch samples
     uint32_t warm_bcap = 0;              // keys per hash bucket
     int cus = 0;                         // compute units: k_fold_ring grid
     void* ingest = nullptr;              // streaming text ingestion state (parse.hip), freed by ingest_free
-    uint2* fscratch = nullptr;           // partition pre-filter: per-workgroup survivor regions
-    size_t fscratch_bytes = 0;
-    void* fstage = nullptr;              // ... and the device copy of host edge batches
-    size_t fstage_bytes = 0;
+    DevBuf<uint2> fscratch;              // partition pre-filter: per-workgroup survivor regions
+    DevBuf<> fstage;                     // ... and the device copy of host edge batches
     void (*ingest_free)(void*) = nullptr;
     // GS_CC_SPARSE_IDS: id -> slot table; cap (above) = slots = 2^hbits + 1
     bool sparse = false;
-    int64_t* keys = nullptr;             // 2^hbits slot keys (INT64_MIN = empty)
+    DevBuf<int64_t> keys;                // 2^hbits slot keys (INT64_MIN = empty)
     uint32_t hbits = 0;
-    unsigned long long* nkeys = nullptr; // distinct ids inserted
-    int64_t* minkey = nullptr;           // per root: minimum id of its component (emission)
+    DevBuf<unsigned long long> nkeys;    // distinct ids inserted
+    DevBuf<int64_t> minkey;              // per root: minimum id of its component (emission)
     bool minkey_valid = false;
     // instrumentation
     bool timing = false;
     uint32_t timing_mask = ~0u;          // kernels timed while timing (bit GS_K_*)
     int fold_timer = GS_K_FOLD;          // GS_K_MERGE while folding an exported partial summary
-    struct Pend { int k; hipEvent_t a, b; uint64_t units; };
+    struct Pend { int k; Event a, b; uint64_t units; };
     std::vector<Pend> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;
     double total_ms[GS_K_COUNT] = {};
     uint64_t launches[GS_K_COUNT] = {};
     uint64_t units[GS_K_COUNT] = {};     // edges (folds, merges) or vertices (closes) the timed launches took
@@ -159,38 +160,44 @@ int check(gs_cc_t* h) {
     return GS_OK;
 }
 
-int ensure_buf(void** p, size_t* have, size_t need) {
-    if (*have >= need) return GS_OK;
-    if (*p) { GS_HIP(hipFree(*p)); *p = nullptr; *have = 0; }
-    if (hipMalloc(p, need) != hipSuccess) { (void)hipGetLastError(); return fail(GS_ERR_NOMEM, "hipMalloc(%zu) failed", need); }
-    *have = need;
-    return GS_OK;
-}
-
-hipEvent_t get_event(gs_cc_t* h) {
-    if (!h->pool.empty()) { hipEvent_t e = h->pool.back(); h->pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
+Event get_event(gs_cc_t* h) {
+    Event e;
+    if (!h->pool.empty()) { e = std::move(h->pool.back()); h->pool.pop_back(); }
+    else (void)e.create(hipEventDefault);
     return e;
 }
 
+// The control block: the words of h->derr (kCtlWords of them, zeroed at creation, words
+// kGiantSlots..kWarmValid set again by gs_cc_reset). The kernels receive pointers to single words.
+enum Ctl : uint32_t {
+    kErrFlags = 0,     // deferred device error flags (RangeCheck, SparseArgs): bit 0 an id out of range,
+                       // bit 1 a sparse-id table full; read and cleared by sync_and_check
+    kGiantSlots = 1,   // two giant slots of two words, [giant root, the root gbits was built for]
+                       // (cc_kernels.hpp "Giant-component state"): close c reads slot c & 1 and writes
+                       // slot (c + 1) & 1; kInvalid = none
+    kHotOwner = 5,     // the root of the component the hot set's entries belong to (kInvalid: none yet)
+    kHotBudget = 6,    // hot-set admission budget: launches that may still admit (kHotAdmitLaunches)
+    kWarmValid = 7,    // != 0: the warm set is built for the current giant
+    // the young k_fold's dynamic chunk counter (u64), an atomicAdd per chunk from every workgroup:
+    // on a 128-B line of its own, away from the giant state every union reads (sharing its line made
+    // a hoisted read of the giant root 2.6x slower in window 1, profiles/r02_h)
+    kWorkWord = 32,
+    kCtlWords = 64
+};
+// words of the pinned mirror h->hscratch that are not a call's results (those start at word 0)
+constexpr int kHostFilterCount = 5;   // gs_cc_filter_edges: the survivor count
+constexpr int kHostErr = 7;           // sync_and_check: the copy of kErrFlags
+constexpr size_t kMarkCtrWords = 3;   // h->mark_ctr (cc_kernels.hpp k_export_log)
+
+inline uint32_t* giant_state(gs_cc_t* h) { return h->derr + kGiantSlots + 2 * (h->closes & 1); }
+
 // Times one span of launches of kernel class k (HIP events on the launch stream). Launch the
 // span's first kernel with start() and its last with stop() through klaunch().
-// the current giant-state slot (cc_kernels.hpp): derr[1 + 2 * (closes & 1)] = giant, [+1] = built;
-// close c reads slot c & 1 and writes slot (c + 1) & 1; derr[5] = hot set owner, derr[6] = hot
-// set admission budget, derr[7] = warm set valid
-inline uint32_t* giant_state(gs_cc_t* h) { return h->derr + 1 + 2 * (h->closes & 1); }
-// derr[kWorkWord..+1]: the young k_fold's dynamic chunk counter, an atomicAdd per chunk from every
-// workgroup: on a 128-B line of its own, away from the giant state every union reads (sharing
-// its line made a hoisted read of the giant root 2.6x slower in window 1, profiles/r02_h)
-constexpr uint32_t kWorkWord = 32;
-constexpr size_t kDerrBytes = 256;
-
 // The events ride on the kernel dispatches themselves (hipExtLaunchKernelGGL start/stop events):
 // separate hipEventRecord marker packets are barrier packets, ~10 us of idle GPU each on gfx950
 // (profiles/r01_v3).
 struct KTimer {
-    gs_cc_t* h; int k; hipEvent_t a = nullptr, b = nullptr; uint64_t units;
+    gs_cc_t* h; int k; Event a, b; uint64_t units;
     KTimer(gs_cc_t* h_, int k_, uint64_t units_ = 0) : h(h_), k(k_), units(units_) {
         if (!h->timing || !(h->timing_mask & (1u << k))) return;
         a = get_event(h);
@@ -199,9 +206,16 @@ struct KTimer {
     hipEvent_t start() const { return a; }
     hipEvent_t stop() const { return b; }
     ~KTimer() {
-        if (a) h->pending.push_back({k, a, b, units});
+        if (a) h->pending.push_back({k, std::move(a), std::move(b), units});
     }
 };
+
+// the arguments every fold kernel takes; a call site sets the fields in which it differs
+inline FoldArgs fold_args(gs_cc_t* h, uint64_t n) {
+    FoldArgs f{n, h->parent, h->mark, h->sbits, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, h->dstats};
+    f.mark_len = h->mark_ctr;
+    return f;
+}
 
 // hipLaunchKernelGGL with optional start/stop events attached to the dispatch
 template <typename F, typename... Args>
@@ -218,21 +232,21 @@ int resolve_timing(gs_cc_t* h) {
         h->total_ms[p.k] += ms;
         h->launches[p.k] += 1;
         h->units[p.k] += p.units;
-        h->pool.push_back(p.a);
-        h->pool.push_back(p.b);
+        h->pool.push_back(std::move(p.a));
+        h->pool.push_back(std::move(p.b));
     }
     h->pending.clear();
     return GS_OK;
 }
 
 int sync_and_check(gs_cc_t* h) {
-    uint32_t* hflag = reinterpret_cast<uint32_t*>(h->hscratch + 7);
-    GS_HIP(hipMemcpyAsync(hflag, h->derr, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    uint32_t* hflag = reinterpret_cast<uint32_t*>(h->hscratch + kHostErr);
+    GS_HIP(hipMemcpyAsync(hflag, h->derr + kErrFlags, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
     GS_HIP(hipStreamSynchronize(h->stream));
     if (*hflag) {
         const uint32_t f = *hflag;
         *hflag = 0;
-        GS_HIP(hipMemsetAsync(h->derr, 0, sizeof(uint32_t), h->stream));
+        GS_HIP(hipMemsetAsync(h->derr + kErrFlags, 0, sizeof(uint32_t), h->stream));
         if (f & 2u)
             return fail(GS_ERR_CAPACITY, "more than %llu distinct ids were folded into a sparse-id summary",
                         (unsigned long long)h->cfg.vertex_capacity);
@@ -359,10 +373,8 @@ static const DebugEnv& dbg() {
 }
 
 static void ensure_stats(gs_cc_t* h) {
-    if (dbg().fold_stats && !h->dstats) {
-        (void)hipMalloc(&h->dstats, 8 * sizeof(unsigned long long));
+    if (dbg().fold_stats && !h->dstats && h->dstats.grow(8, "fold stats") == GS_OK)
         (void)hipMemsetAsync(h->dstats, 0, 8 * sizeof(unsigned long long), h->stream);
-    }
 }
 
 // Vertices a ring fold claims straight under the giant root go to their own bitmap (cbits); the
@@ -388,8 +400,7 @@ void launch_fold(gs_cc_t* h, const void* a, const void* b, uint64_t n, bool youn
                                                                   grid_for((n + ept - 1) / ept, kFoldThreads, 1u << 20))
                                   : grid_for((n + ept - 1) / ept, kFoldThreads, 16384);
     ensure_stats(h);
-    FoldArgs f{n, h->parent, h->mark, h->sbits, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, h->dstats};
-    f.mark_len = h->mark_ctr;
+    FoldArgs f = fold_args(h, n);
     f.combine = (AOS && dbg().pair_combine) ? 1u : 0u;   // pair / survivor folds (combine_hooks)
     if (AOS) f.halve = dbg().pair_halve;
     // hooked roots marked (while no giant exists, k_fold) by mature SoA launches only: in the young
@@ -447,7 +458,7 @@ static void launch_warm_build(gs_cc_t* h, hipEvent_t stop, hipStream_t s) {
     klaunch(k_warm_part, dim3((unsigned)((w.keys_cap + kWarmPartTile - 1) / kWarmPartTile)), dim3(1024), s, nullptr,
             nullptr, w);
     klaunch(k_warm_count, dim3(w.nbk), dim3(1024), s, nullptr, nullptr, w);
-    klaunch(k_warm_done, dim3(1), dim3(1024), s, nullptr, stop, w, h->derr + 7);
+    klaunch(k_warm_done, dim3(1), dim3(1024), s, nullptr, stop, w, h->derr + kWarmValid);
 }
 
 static WarmBuild warm_build_args(gs_cc_t* h) {
@@ -462,7 +473,7 @@ static WarmBuild warm_build_args(gs_cc_t* h) {
     w.nbk = 1u << (h->hot_bits - kWarmLocalBits);
     w.warm = h->warm;
     w.wb = h->warm_bits;
-    w.valid = h->derr + 7;
+    w.valid = h->derr + kWarmValid;
     return w;
 }
 
@@ -472,7 +483,7 @@ static WarmBuild warm_build_args(gs_cc_t* h) {
 static HotArgs ring_hot_args(gs_cc_t* h, bool* build_out) {
     HotArgs hot{h->hot, h->hot_bits, h->hot_cand};
     hot.sample_edges = kHotSampleEdges;
-    hot.budget = h->derr + 6;
+    hot.budget = h->derr + kHotBudget;
     hot.periodic = (h->ring_launches % kHotAdmitEvery == kHotAdmitEvery - 1) ? 1u : 0u;
     ++h->ring_launches;
     hot.five = (h->hot_bits <= kHotBucketBits + 12) ? 1u : 0u;
@@ -481,8 +492,8 @@ static HotArgs ring_hot_args(gs_cc_t* h, bool* build_out) {
     const bool build = h->warm && launch_no >= kWarmAt && (launch_no - kWarmAt) % kWarmEvery == 0;
     hot.warm = h->warm;
     hot.warm_bits = h->warm_bits;
-    hot.warm_valid = h->derr + 7;
-    hot.wkeys = build ? h->wkeys : nullptr;
+    hot.warm_valid = h->derr + kWarmValid;
+    hot.wkeys = build ? h->wkeys.get() : nullptr;
     hot.wctl = h->wctl;
     hot.count_edges = build ? h->warm_sample : 0;
     hot.clocks = dbg().ring_clocks ? 1u : 0u;
@@ -499,9 +510,8 @@ void launch_fold_ring(gs_cc_t* h, const IdT* a, const IdT* b, uint64_t n) {
     // for the current giant (device-gated)
     bool build = false;
     const HotArgs hot = ring_hot_args(h, &build);
-    FoldArgs f{n, h->parent, h->mark, h->sbits, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, h->dstats};
-    f.mark_len = h->mark_ctr;
-    f.cbits = kUseCbits ? h->cbits : nullptr;
+    FoldArgs f = fold_args(h, n);
+    f.cbits = kUseCbits ? h->cbits.get() : nullptr;
     if (h->hkbits[0]) f.hbits = h->hkbits[h->closes & 1];
     else h->hkbits_ok = false;
     h->ilist_ok = false;
@@ -613,8 +623,7 @@ void launch_fold_sparse(gs_cc_t* h, const int64_t* a, const int64_t* b, uint64_t
         uint64_t m = n - off;
         if (h->edges_since_reset < young_limit)
             m = std::min(m, std::max<uint64_t>(std::min(kSparseYoungChunk, young_limit - h->edges_since_reset), 1));
-        FoldArgs f{m, h->parent, h->mark, h->sbits, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, h->dstats};
-        f.mark_len = h->mark_ctr;
+        const FoldArgs f = fold_args(h, m);
         const unsigned grid = grid_for((m + 1) / 2, 256, 16384);
         KTimer t(h, h->fold_timer);
         const int64_t* pa = a + (aos ? 2 * off : off);
@@ -671,34 +680,29 @@ int fold_impl(gs_cc_t* h, const void* a, const void* b, uint64_t n, bool aos, ui
     // double-buffered staging. Chunk i is copied into slot i & 1 on the copy stream while chunk
     // i - 1 folds on the handle's stream; a slot is refilled only after the fold that read it.
     const uint64_t chunk = h->cfg.staging_edges ? h->cfg.staging_edges : kStagingEdges;
-    GS_TRY(ensure_buf(&h->stage, &h->stage_bytes, (size_t)chunk * esz * 4));
-    if (!h->copy) {
-        GS_HIP(hipStreamCreateWithFlags(&h->copy, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            GS_HIP(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
-            GS_HIP(hipEventCreateWithFlags(&h->freed[k], hipEventDisableTiming));
-        }
-    }
-    GS_HIP(hipEventRecord(h->freed[0], h->stream));      // folds queued before this call may still read
-    GS_HIP(hipEventRecord(h->freed[1], h->stream));      // the slots
+    GS_TRY(h->stage.grow((size_t)chunk * esz * 4, "fold: staging"));
+    gs_cc::Staging& sg = h->sg;
+    if (!sg.copy) GS_TRY(make_whole(sg));
+    GS_HIP(hipEventRecord(sg.freed[0], h->stream));      // folds queued before this call may still read
+    GS_HIP(hipEventRecord(sg.freed[1], h->stream));      // the slots
     uint64_t i = 0;
     for (uint64_t off = 0; off < n; off += chunk, ++i) {
         const uint64_t m = (n - off < chunk) ? (n - off) : chunk;
         const int k = (int)(i & 1);
-        char* s0 = static_cast<char*>(h->stage) + (size_t)k * chunk * esz * 2;
+        char* s0 = static_cast<char*>(h->stage.get()) + (size_t)k * chunk * esz * 2;
         char* s1 = s0 + (size_t)chunk * esz;
-        GS_HIP(hipStreamWaitEvent(h->copy, h->freed[k], 0));
+        GS_HIP(hipStreamWaitEvent(sg.copy, sg.freed[k], 0));
         if (aos) {
-            GS_HIP(hipMemcpyAsync(s0, static_cast<const char*>(a) + off * esz * 2, m * esz * 2, hipMemcpyHostToDevice, h->copy));
+            GS_HIP(hipMemcpyAsync(s0, static_cast<const char*>(a) + off * esz * 2, m * esz * 2, hipMemcpyHostToDevice, sg.copy));
         } else {
-            GS_HIP(hipMemcpyAsync(s0, static_cast<const char*>(a) + off * esz, m * esz, hipMemcpyHostToDevice, h->copy));
-            GS_HIP(hipMemcpyAsync(s1, static_cast<const char*>(b) + off * esz, m * esz, hipMemcpyHostToDevice, h->copy));
+            GS_HIP(hipMemcpyAsync(s0, static_cast<const char*>(a) + off * esz, m * esz, hipMemcpyHostToDevice, sg.copy));
+            GS_HIP(hipMemcpyAsync(s1, static_cast<const char*>(b) + off * esz, m * esz, hipMemcpyHostToDevice, sg.copy));
         }
-        GS_HIP(hipEventRecord(h->staged[k], h->copy));
-        GS_HIP(hipStreamWaitEvent(h->stream, h->staged[k], 0));
+        GS_HIP(hipEventRecord(sg.staged[k], sg.copy));
+        GS_HIP(hipStreamWaitEvent(h->stream, sg.staged[k], 0));
         GS_TRY(launch_fold_any(h, s0, s1, m, aos, id_bits));
         GS_HIP(hipGetLastError());
-        GS_HIP(hipEventRecord(h->freed[k], h->stream));
+        GS_HIP(hipEventRecord(sg.freed[k], h->stream));
     }
     return GS_OK;
 }
@@ -798,8 +802,9 @@ int compress_impl(gs_cc_t* h) {
                     in, (int)force);
         ++h->closes;
         // (the close about to run is number closes - 1 now: it reads the marks of its parity)
-        const uint32_t* hb_in = (h->hkbits[0] && h->hkbits_ok) ? h->hkbits[(h->closes - 1) & 1] : nullptr;
-        uint32_t* hb_next = h->hkbits[0] ? h->hkbits[h->closes & 1] : nullptr;
+        const uint32_t* hb_in = (h->hkbits[0] && h->hkbits_ok) ? h->hkbits[(h->closes - 1) & 1].get() : nullptr;
+        uint32_t* hb_next = h->hkbits[0] ? h->hkbits[h->closes & 1].get() : nullptr;
+        uint32_t* cb = kUseCbits ? h->cbits.get() : nullptr;
         // k_compress_list while lists are in use: the last close built an NGL (this one may be a list
         // close) or this one builds one. Its control words are stale after plain closes: cleared
         // (LVALID 0, counts 0) when it starts again
@@ -808,12 +813,13 @@ int compress_impl(gs_cc_t* h) {
         if (lists) {
             if (!h->list_kernel) GS_HIP(hipMemsetAsync(h->lctl, 0, ListCtl::kWords * sizeof(uint32_t), h->stream));
             klaunch(k_compress_list, dim3(grid), dim3(256), h->stream, pick ? nullptr : t.start(), t.stop(),
-                    h->parent, h->cap, h->gbits, h->sbits, (const uint32_t*)in, giant_state(h), h->derr + 5, h->hot,
-                    (int)h->sbits_stale, kUseCbits ? h->cbits : nullptr, h->dbits, samp_in, samp_out, hb_in, hb_next, lc);
+                    h->parent.get(), h->cap, h->gbits.get(), h->sbits.get(), (const uint32_t*)in, giant_state(h),
+                    h->derr + kHotOwner, h->hot.get(), (int)h->sbits_stale, cb, h->dbits.get(), samp_in, samp_out, hb_in,
+                    hb_next, lc);
         } else {
             klaunch(k_compress, dim3(grid_for(h->cap, 1024, kCompressGrid)), dim3(256), h->stream, pick ? nullptr : t.start(),
-                    t.stop(), h->parent, h->cap, h->gbits, h->sbits, (const uint32_t*)in, giant_state(h), h->derr + 5,
-                    h->hot, (int)h->sbits_stale, kUseCbits ? h->cbits : nullptr, h->dbits, samp_in, samp_out, hb_in, hb_next);
+                    t.stop(), h->parent.get(), h->cap, h->gbits.get(), h->sbits.get(), (const uint32_t*)in, giant_state(h),
+                    h->derr + kHotOwner, h->hot.get(), (int)h->sbits_stale, cb, h->dbits.get(), samp_in, samp_out, hb_in, hb_next);
         }
         h->list_kernel = lists;
         h->sbits_stale = false;
@@ -839,23 +845,15 @@ int ensure_minkey(gs_cc_t* h) {
 }
 
 int stats_impl(gs_cc_t* h, bool checksum, uint64_t* nv, uint64_t* nc, uint64_t* sum) {
-    if (h->sparse && checksum) {
-        GS_TRY(ensure_minkey(h));
-        GS_HIP(hipMemsetAsync(h->dscratch, 0, 3 * sizeof(unsigned long long), h->stream));
-        hipLaunchKernelGGL(k_stats_sparse, dim3(grid_for(h->cap, 256, 4096)), dim3(256), 0, h->stream,
-                           (const uint32_t*)h->parent, h->cap, sparse_args(h), (const int64_t*)h->minkey, h->dscratch);
-        GS_HIP(hipGetLastError());
-        GS_HIP(hipMemcpyAsync(h->hscratch, h->dscratch, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
-        GS_TRY(sync_and_check(h));
-        if (nv) *nv = h->hscratch[0];
-        if (nc) *nc = h->hscratch[1];
-        if (sum) *sum = h->hscratch[2];
-        return GS_OK;
-    }
+    const bool by_id = h->sparse && checksum;        // sparse ids: the checksum is over ids, not slots
+    if (by_id) GS_TRY(ensure_minkey(h));
     GS_HIP(hipMemsetAsync(h->dscratch, 0, 3 * sizeof(unsigned long long), h->stream));
     const dim3 grid(grid_for(h->cap, 256, 4096));
-    if (checksum) hipLaunchKernelGGL(k_stats<true>, grid, dim3(256), 0, h->stream, h->parent, h->cap, h->dscratch);
-    else hipLaunchKernelGGL(k_stats<false>, grid, dim3(256), 0, h->stream, h->parent, h->cap, h->dscratch);
+    if (by_id)
+        hipLaunchKernelGGL(k_stats_sparse, grid, dim3(256), 0, h->stream, (const uint32_t*)h->parent, h->cap,
+                           sparse_args(h), (const int64_t*)h->minkey, h->dscratch.get());
+    else if (checksum) hipLaunchKernelGGL(k_stats<true>, grid, dim3(256), 0, h->stream, h->parent.get(), h->cap, h->dscratch.get());
+    else hipLaunchKernelGGL(k_stats<false>, grid, dim3(256), 0, h->stream, h->parent.get(), h->cap, h->dscratch.get());
     GS_HIP(hipGetLastError());
     GS_HIP(hipMemcpyAsync(h->hscratch, h->dscratch, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
     GS_TRY(sync_and_check(h));
@@ -864,6 +862,8 @@ int stats_impl(gs_cc_t* h, bool checksum, uint64_t* nv, uint64_t* nc, uint64_t* 
     if (sum) *sum = h->hscratch[2];
     return GS_OK;
 }
+
+int grow_tmp(gs_cc_t* h, size_t bytes) { return h->tmp.grow(bytes, "emission temporaries"); }
 
 // copy n bytes of device data to dst (device or host)
 int copy_out(gs_cc_t* h, void* dst, const void* src, size_t n) {
@@ -883,8 +883,8 @@ int emit_pairs_sparse(gs_cc_t* h, void* vertices, void* labels, uint64_t cap, ui
         GS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const int64_t*)nullptr, (int64_t*)nullptr,
                                                    (const int64_t*)nullptr, (int64_t*)nullptr, (int)nv, 0, 64, h->stream));
         const size_t arr = ((nv * 8) + 255) & ~(size_t)255;
-        GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, 256 + 4 * arr + sort_bytes));
-        char* base = static_cast<char*>(h->tmp);
+        GS_TRY(grow_tmp(h, 256 + 4 * arr + sort_bytes));
+        char* base = static_cast<char*>(h->tmp.get());
         auto* counter = reinterpret_cast<unsigned long long*>(base);
         auto* ki = reinterpret_cast<int64_t*>(base + 256);
         auto* li = reinterpret_cast<int64_t*>(base + 256 + arr);
@@ -915,10 +915,10 @@ int find_sparse(gs_cc_t* h, const int64_t* ids, int64_t* roots, uint8_t* found, 
     int64_t* dr = roots;
     uint8_t* df = found;
     if (!dev) {
-        GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, 2 * n * 8 + n));
-        di = static_cast<const int64_t*>(h->tmp);
-        dr = static_cast<int64_t*>(h->tmp) + n;
-        df = found ? reinterpret_cast<uint8_t*>(static_cast<int64_t*>(h->tmp) + 2 * n) : nullptr;
+        GS_TRY(grow_tmp(h, 2 * n * 8 + n));
+        di = static_cast<const int64_t*>(h->tmp.get());
+        dr = static_cast<int64_t*>(h->tmp.get()) + n;
+        df = found ? reinterpret_cast<uint8_t*>(static_cast<int64_t*>(h->tmp.get()) + 2 * n) : nullptr;
         GS_HIP(hipMemcpyAsync(const_cast<int64_t*>(di), ids, n * 8,
                               is_device_pointer(ids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
@@ -960,7 +960,8 @@ int cc_fold_slots(gs_cc_t* h, const uint32_t* slots, uint64_t slot_words, int ns
     }
     h->compressed = false;
     h->minkey_valid = false;
-    FoldArgs f{0, h->parent, nullptr, h->sbits, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, nullptr};
+    FoldArgs f = fold_args(h, 0);
+    f.mark = nullptr;
     f.combine = dbg().pair_combine ? 1u : 0u;        // (combine_hooks)
     f.halve = dbg().pair_halve;
     KTimer t(h, GS_K_MERGE);
@@ -1003,40 +1004,15 @@ int cc_filter_async(gs_cc_t* h, const void* a, const void* b, uint64_t n, void* 
     const uint64_t stride = (uint64_t)grid * kHotThreads;                       // groups per round
     // edges per workgroup of the largest launch (the first): its rounds x 4096
     const uint64_t region = (((std::min(n, kFilterChunk) + 3) / 4 + stride - 1) / stride) * (uint64_t)kHotThreads * 4;
-    const size_t need = (size_t)grid * region * sizeof(uint2);
-    if (h->fscratch_bytes < need) {
-        if (h->fscratch) {
-            GS_HIP(hipStreamSynchronize(h->stream));
-            GS_HIP(hipFree(h->fscratch));
-            h->fscratch = nullptr;
-            h->fscratch_bytes = 0;
-        }
-        if (hipMalloc(&h->fscratch, need) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GS_ERR_NOMEM, "partition pre-filter scratch of %zu bytes", need);
-        }
-        h->fscratch_bytes = need;
-    }
+    GS_TRY(h->fscratch.grow((size_t)grid * region, "partition pre-filter scratch", h->stream));
     const size_t esz = h->cfg.id_bits / 8;
     const bool hot_on = h->hot && use_ring(h);
     uint2* o = static_cast<uint2*>(out);
     if (!is_device_pointer(a) || !is_device_pointer(b)) {
         // host edges: staged through a device copy of the batch (the pre-filter reads device memory)
         const size_t bytes = (size_t)n * esz;
-        if (h->fstage_bytes < 2 * bytes) {
-            if (h->fstage) {
-                GS_HIP(hipStreamSynchronize(h->stream));
-                GS_HIP(hipFree(h->fstage));
-                h->fstage = nullptr;
-                h->fstage_bytes = 0;
-            }
-            if (hipMalloc(&h->fstage, 2 * bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(GS_ERR_NOMEM, "partition pre-filter staging of %zu bytes", 2 * bytes);
-            }
-            h->fstage_bytes = 2 * bytes;
-        }
-        char* da = static_cast<char*>(h->fstage);
+        GS_TRY(h->fstage.grow(2 * bytes, "partition pre-filter staging", h->stream));
+        char* da = static_cast<char*>(h->fstage.get());
         GS_HIP(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, h->stream));
         GS_HIP(hipMemcpyAsync(da + bytes, b, bytes, hipMemcpyHostToDevice, h->stream));
         a = da;
@@ -1047,7 +1023,8 @@ int cc_filter_async(gs_cc_t* h, const void* a, const void* b, uint64_t n, void* 
         const char* pa = static_cast<const char*>(a) + off * esz;
         const char* pb = static_cast<const char*>(b) + off * esz;
         const int aligned = ((reinterpret_cast<uintptr_t>(pa) | reinterpret_cast<uintptr_t>(pb)) & 15) == 0;
-        FoldArgs f{m, h->parent, nullptr, nullptr, h->gbits, giant_state(h), RangeCheck{h->cap, h->derr}, nullptr};
+        FoldArgs f = fold_args(h, m);
+        f.mark = f.sbits = nullptr;
         bool build = false;
         HotArgs hot{};
         if (hot_on) hot = ring_hot_args(h, &build);
@@ -1056,7 +1033,7 @@ int cc_filter_async(gs_cc_t* h, const void* a, const void* b, uint64_t n, void* 
         hipEvent_t stop = build ? nullptr : t.stop();
 #define GS_LAUNCH_FILTER(IDT, HOTV)                                                                                \
     klaunch(k_filter_out<IDT, HOTV>, gd, dim3(kHotThreads), h->stream, t.start(), stop, (const IDT*)pa, (const IDT*)pb, \
-            f, hot, h->fscratch, region, o, dcount, aligned)
+            f, hot, h->fscratch.get(), region, o, dcount, aligned)
         if (h->cfg.id_bits == 32) { if (hot_on) GS_LAUNCH_FILTER(uint32_t, true); else GS_LAUNCH_FILTER(uint32_t, false); }
         else { if (hot_on) GS_LAUNCH_FILTER(int64_t, true); else GS_LAUNCH_FILTER(int64_t, false); }
 #undef GS_LAUNCH_FILTER
@@ -1087,8 +1064,8 @@ int cc_filter_state(gs_cc_t* h, uint32_t** gbits, uint64_t* gbits_bytes, uint32_
 int cc_install_giant(gs_cc_t* h, const uint32_t* words) {
     GS_TRY(check(h));
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(k_install_giant, dim3(1), dim3(1024), 0, h->stream, words, giant_state(h), h->derr + 5,
-                       (h->hot && use_ring(h)) ? h->hot : nullptr);
+    hipLaunchKernelGGL(k_install_giant, dim3(1), dim3(1024), 0, h->stream, words, giant_state(h), h->derr + kHotOwner,
+                       (h->hot && use_ring(h)) ? h->hot.get() : nullptr);
     GS_HIP(hipGetLastError());
     return GS_OK;
 }
@@ -1159,59 +1136,45 @@ int gs_cc_create(gs_cc_t** out, const gs_cc_config* cfg) {
         while ((1ull << h->hbits) < 2 * cfg->vertex_capacity) ++h->hbits;
         h->cap = (1u << h->hbits) + 1;
     }
-    auto bail = [&](int rc) { gs_cc_destroy(h); return rc; };
-    if (hipStreamCreateWithFlags(&h->own, hipStreamNonBlocking) != hipSuccess) return bail(fail(GS_ERR_HIP, "hipStreamCreate failed"));
+    struct Destroy { void operator()(gs_cc_t* p) const { (void)gs_cc_destroy(p); } };
+    std::unique_ptr<gs_cc_t, Destroy> guard(h);      // a failure below destroys what exists so far
+    GS_TRY(h->own.create());
     h->stream = h->own;
-    if (hipMalloc(&h->parent, (size_t)h->cap * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(GS_ERR_NOMEM, "parent[%u] allocation failed", h->cap)); }
+    const size_t bit_words = mark_bytes(h->cap) / 4;
+    GS_TRY(h->parent.grow(h->cap, "gs_cc_create: parent"));
     if (cfg->flags & GS_CC_TRACK_MARKS) {
-        if (hipMalloc(&h->mark_buf, (size_t)h->cap * 2 * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return bail(fail(GS_ERR_NOMEM, "hook log allocation failed")); }
-        if (hipMalloc(&h->mark_ctr, 128) != hipSuccess) { (void)hipGetLastError(); return bail(fail(GS_ERR_NOMEM, "hook log counter allocation failed")); }
+        GS_TRY(h->mark_buf.grow((size_t)h->cap * 2, "gs_cc_create: hook log"));
+        GS_TRY(h->mark_ctr.grow(128 / sizeof(unsigned long long), "gs_cc_create: hook log counter"));
         h->mark = h->mark_buf;
     }
-    if (hipMalloc(&h->gbits, mark_bytes(h->cap)) != hipSuccess || hipMalloc(&h->sbits, mark_bytes(h->cap)) != hipSuccess ||
-        hipMalloc(&h->cbits, mark_bytes(h->cap)) != hipSuccess ||
-        hipMalloc(&h->derr, kDerrBytes) != hipSuccess || hipMalloc(&h->psamp, 2 * kPickSamples * sizeof(uint32_t)) != hipSuccess || hipMalloc(&h->dscratch, 8 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(&h->hscratch, 8 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return bail(fail(GS_ERR_NOMEM, "scratch allocation failed"));
-    }
+    for (auto* b : {&h->gbits, &h->sbits, &h->cbits}) GS_TRY(b->grow(bit_words, "gs_cc_create: bitmap"));
+    GS_TRY(h->derr.grow(kCtlWords, "gs_cc_create: control block"));
+    GS_TRY(h->psamp.grow(2 * kPickSamples, "gs_cc_create: giant samples"));
+    GS_TRY(h->dscratch.grow(8, "gs_cc_create: scratch"));
+    GS_TRY(h->hscratch.alloc(8, "gs_cc_create: scratch"));
     std::memset(h->hscratch, 0, 8 * sizeof(unsigned long long));
-    if (!sparse && (hipMalloc(&h->hkbits[0], mark_bytes(h->cap)) != hipSuccess ||
-                    hipMalloc(&h->hkbits[1], mark_bytes(h->cap)) != hipSuccess)) {
-        (void)hipGetLastError();
-        return bail(fail(GS_ERR_NOMEM, "hooked-root bitmaps allocation failed"));
-    }
     if (!sparse) {
+        for (auto& hb : h->hkbits) GS_TRY(hb.grow(bit_words, "gs_cc_create: hooked-root bitmap"));
         // NGL: up to capacity/64 vertices outside the giant (more: bitmap closes); touch log:
         // kTlogSlots slots per interval
         h->ngl_sub = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(64, (uint64_t)h->cap / 64 / kListSub));
-        if (hipMalloc(&h->lctl, ListCtl::kWords * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc(&h->ngl[0], (size_t)kListSub * h->ngl_sub * sizeof(uint2)) != hipSuccess ||
-            hipMalloc(&h->ngl[1], (size_t)kListSub * h->ngl_sub * sizeof(uint2)) != hipSuccess ||
-            hipMalloc(&h->tlog[0], (size_t)kTlogSlots * kSlotWords * 4) != hipSuccess ||
-            hipMalloc(&h->tlog[1], (size_t)kTlogSlots * kSlotWords * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return bail(fail(GS_ERR_NOMEM, "list-close buffers allocation failed"));
-        }
-    }
-    if (sparse && (hipMalloc(&h->keys, sizeof(int64_t) << h->hbits) != hipSuccess ||
-                   hipMalloc(&h->minkey, sizeof(int64_t) * (size_t)h->cap) != hipSuccess ||
-                   hipMalloc(&h->nkeys, sizeof(unsigned long long)) != hipSuccess)) {
-        (void)hipGetLastError();
-        return bail(fail(GS_ERR_NOMEM, "sparse id table (2^%u slots) allocation failed", h->hbits));
+        GS_TRY(h->lctl.grow(ListCtl::kWords, "gs_cc_create: list-close control"));
+        for (auto& q : h->ngl) GS_TRY(q.grow((size_t)kListSub * h->ngl_sub, "gs_cc_create: list-close NGL"));
+        for (auto& q : h->tlog) GS_TRY(q.grow((size_t)kTlogSlots * kSlotWords, "gs_cc_create: touch log"));
+    } else {
+        GS_TRY(h->keys.grow((size_t)1 << h->hbits, "gs_cc_create: sparse id table"));
+        GS_TRY(h->minkey.grow(h->cap, "gs_cc_create: sparse id table"));
+        GS_TRY(h->nkeys.grow(1, "gs_cc_create: sparse id table"));
     }
     if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess) h->cus = 0;
     {
         uint32_t bits = 0;
         while (bits < 32 && (1ull << bits) < (uint64_t)h->cap) ++bits;
         if (!sparse && bits >= 20 && bits <= kHotBucketBits + 15) {     // remainders fit 15 bits (+1 in 16)
-            if (hipMalloc(&h->hot, kHotBuckets * sizeof(uint2)) != hipSuccess ||
-                hipMalloc(&h->hot_cand, sizeof(uint32_t) << kHotCandBits) != hipSuccess) {
-                (void)hipGetLastError();
-                if (h->hot) (void)hipFree(h->hot);
-                if (h->hot_cand) (void)hipFree(h->hot_cand);
-                h->hot = nullptr;
-                h->hot_cand = nullptr;
+            // the hot set and the warm set are optional: without their memory the folds do without
+            if (h->hot.grow(kHotBuckets, "hot set") != GS_OK || h->hot_cand.grow((size_t)1 << kHotCandBits, "hot set") != GS_OK) {
+                h->hot.reset();
+                h->hot_cand.reset();
             }
             h->hot_bits = bits;
             // warm set: only where gbits outgrows an XCD's 4 MiB L2 (with the ring fold), its table
@@ -1224,86 +1187,35 @@ int gs_cc_create(gs_cc_t** out, const gs_cc_config* cfg) {
                 h->warm_sample = (h->warm_sample + 255) / 256 * 256;        // whole wave steps
                 const uint64_t keys = 2 * h->warm_sample;
                 h->warm_bcap = (uint32_t)((keys / nbk + keys / nbk / 2 + 1024 + 7) & ~7ull);  // 1.5 x the mean bucket
-                const size_t ctl = sizeof(unsigned long long) + (size_t)nbk * 4;
-                if (hipMalloc(&h->warm, (size_t)4 << h->warm_bits) != hipSuccess ||
-                    hipMalloc(&h->wkeys, keys * 4) != hipSuccess ||
-                    hipMalloc(&h->wpart, (size_t)nbk * h->warm_bcap * 2) != hipSuccess ||
-                    hipMalloc(&h->wctl, ctl) != hipSuccess || hipMemsetAsync(h->wctl, 0, ctl, h->stream) != hipSuccess) {
+                const size_t ctl = 1 + ((size_t)nbk + 1) / 2;               // u64 words: the count, nbk u32 fills
+                if (h->warm.grow((size_t)1 << h->warm_bits, "warm set") != GS_OK || h->wkeys.grow(keys, "warm set") != GS_OK ||
+                    h->wpart.grow((size_t)nbk * h->warm_bcap, "warm set") != GS_OK || h->wctl.grow(ctl, "warm set") != GS_OK ||
+                    hipMemsetAsync(h->wctl, 0, ctl * 8, h->stream) != hipSuccess) {
                     (void)hipGetLastError();
-                    if (h->warm) (void)hipFree(h->warm);
-                    if (h->wkeys) (void)hipFree(h->wkeys);
-                    if (h->wpart) (void)hipFree(h->wpart);
-                    if (h->wctl) (void)hipFree(h->wctl);
-                    h->warm = nullptr;
-                    h->wkeys = nullptr;
-                    h->wpart = nullptr;
-                    h->wctl = nullptr;
+                    h->warm.reset();
+                    h->wkeys.reset();
+                    h->wpart.reset();
+                    h->wctl.reset();
                 }
             }
         }
     }
-    if (hipMemsetAsync(h->derr, 0, kDerrBytes, h->stream) != hipSuccess) return bail(fail(GS_ERR_HIP, "memset failed"));
-    int rc = gs_cc_reset(h);
-    if (rc != GS_OK) return bail(rc);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(GS_ERR_HIP, "stream sync failed"));
-    *out = h;
+    GS_HIP(hipMemsetAsync(h->derr, 0, kCtlWords * sizeof(uint32_t), h->stream));
+    GS_TRY(gs_cc_reset(h));
+    GS_HIP(hipStreamSynchronize(h->stream));
+    *out = guard.release();
     return GS_OK;
 }
 
+// The owners free what the handle holds (owned.hpp); what is left is to let the work finish first:
+// every stream the handle owns or was given is synchronised before anything is freed.
 int gs_cc_destroy(gs_cc_t* h) {
     if (!h) return GS_OK;
     (void)cc_settle(h);                          // peers may wait for this rank in a tail round
     DeviceGuard g(h->device);
-    if (h->own) (void)hipStreamSynchronize(h->own);
-    if (h->stream && h->stream != h->own) (void)hipStreamSynchronize(h->stream);
-    for (auto& p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
-    for (auto e : h->pool) (void)hipEventDestroy(e);
-    if (h->parent) (void)hipFree(h->parent);
-    if (h->mark_buf) (void)hipFree(h->mark_buf);
-    if (h->mark_ctr) (void)hipFree(h->mark_ctr);
-    if (h->derr) (void)hipFree(h->derr);
-    if (h->psamp) (void)hipFree(h->psamp);
-    if (h->gbits) (void)hipFree(h->gbits);
-    if (h->sbits) (void)hipFree(h->sbits);
-    if (h->cbits) (void)hipFree(h->cbits);
-    for (auto* hb : h->hkbits) if (hb) (void)hipFree(hb);
-    if (h->lctl) (void)hipFree(h->lctl);
-    for (auto* q : h->ngl) if (q) (void)hipFree(q);
-    for (auto* q : h->tlog) if (q) (void)hipFree(q);
-    if (h->dbits) (void)hipFree(h->dbits);
-    if (h->elab) (void)hipFree(h->elab);
-    if (h->dstats) (void)hipFree(h->dstats);
-    if (h->fscratch) (void)hipFree(h->fscratch);
-    if (h->fstage) (void)hipFree(h->fstage);
-    if (h->hot) (void)hipFree(h->hot);
-    if (h->hot_cand) (void)hipFree(h->hot_cand);
-    if (h->warm) (void)hipFree(h->warm);
-    if (h->wkeys) (void)hipFree(h->wkeys);
-    if (h->wpart) (void)hipFree(h->wpart);
-    if (h->wctl) (void)hipFree(h->wctl);
-    if (h->keys) (void)hipFree(h->keys);
-    if (h->minkey) (void)hipFree(h->minkey);
-    if (h->nkeys) (void)hipFree(h->nkeys);
-    if (h->dscratch) (void)hipFree(h->dscratch);
-    if (h->hscratch) (void)hipHostFree(h->hscratch);
-    if (h->stage) (void)hipFree(h->stage);
-    if (h->copy) (void)hipStreamSynchronize(h->copy);
-    for (int k = 0; k < 2; ++k) {
-        if (h->staged[k]) (void)hipEventDestroy(h->staged[k]);
-        if (h->freed[k]) (void)hipEventDestroy(h->freed[k]);
-    }
-    if (h->copy) (void)hipStreamDestroy(h->copy);
-    if (h->estream) (void)hipStreamSynchronize(h->estream);
-    for (auto& s : h->eslot) {
-        if (s.mem) (void)hipFree(s.mem);
-        if (s.staged) (void)hipEventDestroy(s.staged);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
-    if (h->ecount) (void)hipHostFree(h->ecount);
-    if (h->estream) (void)hipStreamDestroy(h->estream);
-    if (h->tmp) (void)hipFree(h->tmp);
+    for (hipStream_t s : {h->own.get(), h->stream != h->own.get() ? h->stream : nullptr, h->sg.copy.get(), h->ea.estream.get()})
+        if (s) (void)hipStreamSynchronize(s);
     if (h->ingest && h->ingest_free) h->ingest_free(h->ingest);
-    if (h->own) (void)hipStreamDestroy(h->own);
     delete h;
     return GS_OK;
 }
@@ -1313,11 +1225,11 @@ int gs_cc_reset(gs_cc_t* h) {
     GS_TRY(cc_settle(h));                      // a pending multi-GPU window first (comm.hip)
     DeviceGuard g(h->device);
     GS_HIP(hipMemsetAsync(h->parent, 0xFF, (size_t)h->cap * sizeof(uint32_t), h->stream));
-    if (h->mark_ctr) GS_HIP(hipMemsetAsync(h->mark_ctr, 0, 3 * sizeof(unsigned long long), h->stream));
+    if (h->mark_ctr) GS_HIP(hipMemsetAsync(h->mark_ctr, 0, kMarkCtrWords * sizeof(unsigned long long), h->stream));
     GS_HIP(hipMemsetAsync(h->gbits, 0, mark_bytes(h->cap), h->stream));
     GS_HIP(hipMemsetAsync(h->sbits, 0, mark_bytes(h->cap), h->stream));
     GS_HIP(hipMemsetAsync(h->cbits, 0, mark_bytes(h->cap), h->stream));
-    for (auto* hb : h->hkbits) if (hb) GS_HIP(hipMemsetAsync(hb, 0, mark_bytes(h->cap), h->stream));
+    for (auto& hb : h->hkbits) if (hb) GS_HIP(hipMemsetAsync(hb, 0, mark_bytes(h->cap), h->stream));
     h->hkbits_ok = true;
     h->list_prev = false;
     h->list_kernel = false;
@@ -1329,14 +1241,20 @@ int gs_cc_reset(gs_cc_t* h) {
         GS_HIP(hipMemsetAsync(h->elab, 0xFF, (size_t)h->cap * 4, h->stream));
         GS_HIP(hipMemsetAsync(h->dbits, 0, mark_bytes(h->cap), h->stream));
     }
-    // giant state (cc_kernels.hpp, giant_state()): both slots no giant / gbits built for none,
-    // hot set owner none
-    GS_HIP(hipMemsetAsync(h->derr + 1, 0xFF, 5 * sizeof(uint32_t), h->stream));
+    // the control block (enum Ctl): both giant slots no giant / gbits built for none, hot set owner
+    // none, the full admission budget, warm set not built; the error flags stay
     {
-        static const uint32_t budget = kHotAdmitLaunches;   // derr[6]
-        GS_HIP(hipMemcpyAsync(h->derr + 6, &budget, sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+        static const struct Init {
+            uint32_t w[kWarmValid + 1];
+            Init() {
+                for (uint32_t i = kGiantSlots; i <= kHotOwner; ++i) w[i] = kInvalid;
+                w[kErrFlags] = w[kWarmValid] = 0;
+                w[kHotBudget] = kHotAdmitLaunches;
+            }
+        } init;
+        GS_HIP(hipMemcpyAsync(h->derr + kGiantSlots, init.w + kGiantSlots, (kWarmValid + 1 - kGiantSlots) * sizeof(uint32_t),
+                              hipMemcpyHostToDevice, h->stream));
     }
-    GS_HIP(hipMemsetAsync(h->derr + 7, 0, sizeof(uint32_t), h->stream));      // warm set: not built
     GS_HIP(hipMemsetAsync(h->psamp, 0xFF, 2 * kPickSamples * sizeof(uint32_t), h->stream));   // no samples yet
     if (h->hot) GS_HIP(hipMemsetAsync(h->hot, 0, kHotBuckets * sizeof(uint2), h->stream));
     if (h->hot_cand) GS_HIP(hipMemsetAsync(h->hot_cand, 0xFF, sizeof(uint32_t) << kHotCandBits, h->stream));
@@ -1414,12 +1332,15 @@ int gs_cc_merge(gs_cc_t* into, gs_cc_t* from) {
     if (!into->sparse && from->cap > into->cap)
         return fail(GS_ERR_RANGE, "gs_cc_merge: source capacity %u exceeds target %u", from->cap, into->cap);
     DeviceGuard g(into->device);
-    if (from->stream != into->stream) {
-        hipEvent_t e = get_event(into);
-        GS_HIP(hipEventRecord(e, from->stream));
-        GS_HIP(hipStreamWaitEvent(into->stream, e, 0));
-        into->pool.push_back(e);
-    }
+    // `later` waits for what `first` has queued so far
+    auto order = [into](hipStream_t first, hipStream_t later) {
+        Event e = get_event(into);
+        GS_HIP(hipEventRecord(e, first));
+        GS_HIP(hipStreamWaitEvent(later, e, 0));
+        into->pool.push_back(std::move(e));
+        return (int)GS_OK;
+    };
+    if (from->stream != into->stream) GS_TRY(order(from->stream, into->stream));
     into->compressed = false;
     into->minkey_valid = false;
     into->hkbits_ok = false;
@@ -1427,23 +1348,18 @@ int gs_cc_merge(gs_cc_t* into, gs_cc_t* from) {
     if (into->sparse) {
         KTimer t(into, GS_K_MERGE);
         const dim3 grid(grid_for(from->cap, 256, 16384));
-        FoldArgs f{0, into->parent, into->mark, into->sbits, into->gbits, giant_state(into), RangeCheck{into->cap, into->derr}, nullptr};
-        f.mark_len = into->mark_ctr;
+        const FoldArgs f = fold_args(into, 0);
         if (into->mark) klaunch(k_merge_sparse<true>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, sparse_args(from), f, sparse_args(into));
         else klaunch(k_merge_sparse<false>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, sparse_args(from), f, sparse_args(into));
     } else {
         KTimer t(into, GS_K_MERGE);
         const dim3 grid(grid_for(from->cap, 256, 16384));
-        if (into->mark) klaunch(k_merge_dense<true>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, from->cap, into->parent, into->mark, into->mark_ctr, into->sbits);
-        else klaunch(k_merge_dense<false>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, from->cap, into->parent, into->mark, into->mark_ctr, into->sbits);
+        if (into->mark) klaunch(k_merge_dense<true>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, from->cap, into->parent.get(), into->mark, into->mark_ctr.get(), into->sbits.get());
+        else klaunch(k_merge_dense<false>, grid, dim3(256), into->stream, t.start(), t.stop(), (const uint32_t*)from->parent, from->cap, into->parent.get(), into->mark, into->mark_ctr.get(), into->sbits.get());
     }
     GS_HIP(hipGetLastError());
-    if (from->stream != into->stream) {   // `from` must not be reused before the merge read it
-        hipEvent_t e = get_event(into);
-        GS_HIP(hipEventRecord(e, into->stream));
-        GS_HIP(hipStreamWaitEvent(from->stream, e, 0));
-        into->pool.push_back(e);
-    }
+    // `from` must not be reused before the merge read it
+    if (from->stream != into->stream) GS_TRY(order(into->stream, from->stream));
     return GS_OK;
 }
 
@@ -1538,8 +1454,8 @@ int gs_cc_emit_dense(gs_cc_t* h, void* labels, uint64_t n) {
         hipLaunchKernelGGL(k_widen, dim3(grid_for(m, 256, 16384)), dim3(256), 0, h->stream, h->parent, (int64_t*)labels, m);
         GS_HIP(hipGetLastError());
     } else {
-        GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, m * 8 + 8));
-        hipLaunchKernelGGL(k_widen, dim3(grid_for(m, 256, 16384)), dim3(256), 0, h->stream, h->parent, (int64_t*)h->tmp, m);
+        GS_TRY(grow_tmp(h, m * 8 + 8));
+        hipLaunchKernelGGL(k_widen, dim3(grid_for(m, 256, 16384)), dim3(256), 0, h->stream, h->parent.get(), (int64_t*)h->tmp.get(), m);
         GS_HIP(hipGetLastError());
         GS_TRY(copy_out(h, labels, h->tmp, m * 8));
     }
@@ -1564,9 +1480,9 @@ int gs_cc_emit_pairs(gs_cc_t* h, void* vertices, void* labels, uint64_t cap, uin
     // layout of tmp: [tile counts u32 x ntiles][offsets u64 x ntiles+1][vertices][labels]
     const size_t cnt_b = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
     const size_t off_b = ((size_t)(ntiles + 1) * 8 + 15) & ~(size_t)15;
-    GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, cnt_b + off_b));
-    uint32_t* cnt = static_cast<uint32_t*>(h->tmp);
-    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp) + cnt_b);
+    GS_TRY(grow_tmp(h, cnt_b + off_b));
+    uint32_t* cnt = static_cast<uint32_t*>(h->tmp.get());
+    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp.get()) + cnt_b);
     hipLaunchKernelGGL(k_tile_count, dim3(ntiles), dim3(kTileThreads), 0, h->stream, h->parent, h->cap, cnt);
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, cnt, off, ntiles, (unsigned long long*)nullptr);
     GS_HIP(hipGetLastError());
@@ -1580,13 +1496,13 @@ int gs_cc_emit_pairs(gs_cc_t* h, void* vertices, void* labels, uint64_t cap, uin
         void* vo = vertices;
         void* lo = labels;
         if (!dev) {
-            GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, cnt_b + off_b + 2 * w * esz));
-            cnt = static_cast<uint32_t*>(h->tmp);
-            off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp) + cnt_b);
-            // ensure_buf may have reallocated: recompute the offsets
+            GS_TRY(grow_tmp(h, cnt_b + off_b + 2 * w * esz));
+            cnt = static_cast<uint32_t*>(h->tmp.get());
+            off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp.get()) + cnt_b);
+            // the grow may have reallocated: recompute the offsets
             hipLaunchKernelGGL(k_tile_count, dim3(ntiles), dim3(kTileThreads), 0, h->stream, h->parent, h->cap, cnt);
             hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, cnt, off, ntiles, (unsigned long long*)nullptr);
-            vo = static_cast<char*>(h->tmp) + cnt_b + off_b;
+            vo = static_cast<char*>(h->tmp.get()) + cnt_b + off_b;
             lo = static_cast<char*>(vo) + w * esz;
         }
         if (h->cfg.id_bits == 32)
@@ -1616,14 +1532,13 @@ static int delta_begin(gs_cc_t* h, const char* who, void* vertices, void* labels
     if (h->sparse) return fail(GS_ERR_UNSUPPORTED, "%s: sparse-id summary (use gs_cc_emit_pairs)", who);
     if (!h->elab) {                      // first call: every vertex dirty, nothing emitted yet
         DeviceGuard g(h->device);
-        if (hipMalloc(&h->elab, (size_t)h->cap * 4) != hipSuccess || hipMalloc(&h->dbits, mark_bytes(h->cap)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (h->elab) (void)hipFree(h->elab);
-            h->elab = nullptr;
-            return fail(GS_ERR_NOMEM, "%s: state allocation failed", who);
-        }
-        GS_HIP(hipMemsetAsync(h->elab, 0xFF, (size_t)h->cap * 4, h->stream));
-        GS_HIP(hipMemsetAsync(h->dbits, 0xFF, mark_bytes(h->cap), h->stream));
+        DevBuf<uint32_t> elab, dbits;
+        GS_TRY(elab.grow(h->cap, who));
+        GS_TRY(dbits.grow(mark_bytes(h->cap) / 4, who));
+        GS_HIP(hipMemsetAsync(elab, 0xFF, (size_t)h->cap * 4, h->stream));
+        GS_HIP(hipMemsetAsync(dbits, 0xFF, mark_bytes(h->cap), h->stream));
+        h->elab = std::move(elab);
+        h->dbits = std::move(dbits);
     }
     return GS_OK;
 }
@@ -1640,10 +1555,10 @@ static int delta_enqueue(gs_cc_t* h, uint64_t cap, void* vo, void* lo, unsigned 
     const size_t cnt_b = ((size_t)ntiles * 4 + 15) & ~(size_t)15;
     const size_t off_b = ((size_t)(ntiles + 1) * 8 + 15) & ~(size_t)15;
     const size_t tile_pairs = (size_t)ntiles * kTile;
-    GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, cnt_b + off_b + 2 * tile_pairs * esz));
-    uint32_t* cnt = static_cast<uint32_t*>(h->tmp);
-    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp) + cnt_b);
-    char* sv = static_cast<char*>(h->tmp) + cnt_b + off_b;
+    GS_TRY(grow_tmp(h, cnt_b + off_b + 2 * tile_pairs * esz));
+    uint32_t* cnt = static_cast<uint32_t*>(h->tmp.get());
+    uint64_t* off = reinterpret_cast<uint64_t*>(static_cast<char*>(h->tmp.get()) + cnt_b);
+    char* sv = static_cast<char*>(h->tmp.get()) + cnt_b + off_b;
     char* sl = sv + tile_pairs * esz;
 #define GS_DELTA(IdT)                                                                                                    \
     hipLaunchKernelGGL(k_delta_stage<IdT>, dim3((ntiles + kDeltaTiles - 1) / kDeltaTiles), dim3(kTileThreads), 0,       \
@@ -1651,7 +1566,7 @@ static int delta_enqueue(gs_cc_t* h, uint64_t cap, void* vo, void* lo, unsigned 
                        ntiles, cnt, (IdT*)sv, (IdT*)sl);                                                                   \
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, h->stream, cnt, off, ntiles, total_host);                      \
     hipLaunchKernelGGL(k_delta_pack<IdT>, dim3(ntiles), dim3(256), 0, h->stream, (const IdT*)sv, (const IdT*)sl,           \
-                       (const uint32_t*)cnt, (const uint64_t*)off, ntiles, cap, h->elab, h->dbits, h->cap, (IdT*)vo, (IdT*)lo, \
+                       (const uint32_t*)cnt, (const uint64_t*)off, ntiles, cap, h->elab.get(), h->dbits.get(), h->cap, (IdT*)vo, (IdT*)lo, \
                        total_out)
     if (h->cfg.id_bits == 32) { GS_DELTA(uint32_t); } else { GS_DELTA(int64_t); }
 #undef GS_DELTA
@@ -1688,9 +1603,8 @@ static unsigned emit_copy_blocks() {
 static int delta_slot(gs_cc_t* h, int si, uint64_t cap, char** sv, char** sl) {
     const size_t esz = h->cfg.id_bits / 8;
     const uint64_t scap = std::min<uint64_t>(cap, h->cap);
-    gs_cc::EmitSlot& S = h->eslot[si];
-    GS_TRY(ensure_buf(&S.mem, &S.bytes, 16 + 2 * scap * esz));     // [size word | vertices | labels]
-    *sv = static_cast<char*>(S.mem) + 16;
+    GS_TRY(h->eslot[si].grow(16 + 2 * scap * esz, "delta emission slot"));     // [size word | vertices | labels]
+    *sv = static_cast<char*>(h->eslot[si].get()) + 16;
     *sl = *sv + scap * esz;
     return GS_OK;
 }
@@ -1729,42 +1643,36 @@ int gs_cc_emit_delta_async(gs_cc_t* h, void* vertices, void* labels, uint64_t ca
     GS_TRY(delta_begin(h, "gs_cc_emit_delta_async", vertices, labels, cap, n_out));
     if (h->n_epend >= 2) return fail(GS_ERR_INVALID, "gs_cc_emit_delta_async: two emissions pending (gs_cc_emit_wait first)");
     DeviceGuard g(h->device);
-    if (!h->estream) {
-        GS_HIP(hipStreamCreateWithFlags(&h->estream, hipStreamNonBlocking));
-        GS_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->ecount), 2 * sizeof(unsigned long long), hipHostMallocDefault));
-        for (auto& s : h->eslot) {
-            GS_HIP(hipEventCreateWithFlags(&s.staged, hipEventDisableTiming));
-            GS_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-        }
-    }
+    gs_cc::EmitAsync& ea = h->ea;
+    if (!ea.estream) GS_TRY(make_whole(ea));
     GS_TRY(compress_impl(h));
     const int si = (int)(h->enext & 1u);
     char *sv = nullptr, *sl = nullptr;
     GS_TRY(delta_slot(h, si, cap, &sv, &sl));
     unsigned long long* cdev = nullptr;
-    GS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&cdev), h->ecount, 0));
+    GS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&cdev), ea.ecount, 0));
     const uint64_t* total = nullptr;
     // the size goes to the pinned word from the copy kernel (a host store at the end of the scan
     // cost that kernel ~20 us: the release of a kernel that writes host memory) or, for pageable
     // buffers, by a DMA behind the pack
-    GS_TRY(delta_enqueue(h, cap, sv, sl, nullptr, &total, static_cast<uint64_t*>(h->eslot[si].mem)));
+    GS_TRY(delta_enqueue(h, cap, sv, sl, nullptr, &total, static_cast<uint64_t*>(h->eslot[si].get())));
     // buffers the device can write: copied out right away, on estream, by a few workgroups (their
     // PCIe writes overlap the next fold); pageable ones: by DMA at the wait
     void* dv = cap ? device_view(vertices) : nullptr;
     void* dl = cap ? device_view(labels) : nullptr;
     const bool kcopy = dv && dl;
-    if (!kcopy) GS_HIP(hipMemcpyAsync(h->ecount + si, total, 8, hipMemcpyDeviceToHost, h->stream));
-    GS_HIP(hipEventRecord(h->eslot[si].staged, h->stream));
+    if (!kcopy) GS_HIP(hipMemcpyAsync(ea.ecount + si, total, 8, hipMemcpyDeviceToHost, h->stream));
+    GS_HIP(hipEventRecord(ea.staged[si], h->stream));
     if (kcopy) {
-        GS_HIP(hipStreamWaitEvent(h->estream, h->eslot[si].staged, 0));
+        GS_HIP(hipStreamWaitEvent(ea.estream, ea.staged[si], 0));
         if (h->cfg.id_bits == 32)
-            hipLaunchKernelGGL(k_delta_copy<uint32_t>, dim3(emit_copy_blocks()), dim3(256), 0, h->estream, (const uint32_t*)sv,
+            hipLaunchKernelGGL(k_delta_copy<uint32_t>, dim3(emit_copy_blocks()), dim3(256), 0, ea.estream, (const uint32_t*)sv,
                                (const uint32_t*)sl, total, cap, (uint32_t*)dv, (uint32_t*)dl, cdev + si);
         else
-            hipLaunchKernelGGL(k_delta_copy<int64_t>, dim3(emit_copy_blocks()), dim3(256), 0, h->estream, (const int64_t*)sv,
+            hipLaunchKernelGGL(k_delta_copy<int64_t>, dim3(emit_copy_blocks()), dim3(256), 0, ea.estream, (const int64_t*)sv,
                                (const int64_t*)sl, total, cap, (int64_t*)dv, (int64_t*)dl, cdev + si);
         GS_HIP(hipGetLastError());
-        GS_HIP(hipEventRecord(h->eslot[si].done, h->estream));
+        GS_HIP(hipEventRecord(ea.done[si], ea.estream));
     }
     h->epend[h->n_epend++] = gs_cc::EmitPend{si, n_out, cap, vertices, labels, kcopy};
     ++h->enext;
@@ -1776,21 +1684,22 @@ int gs_cc_emit_wait(gs_cc_t* h, uint32_t keep) {
     DeviceGuard g(h->device);
     const size_t esz = h->cfg.id_bits / 8;
     uint64_t over = 0, over_cap = 0;
+    gs_cc::EmitAsync& ea = h->ea;
     while (h->n_epend > (int)keep) {
         const gs_cc::EmitPend p = h->epend[0];
         for (int i = 1; i < h->n_epend; ++i) h->epend[i - 1] = h->epend[i];
         --h->n_epend;
-        GS_HIP(hipEventSynchronize(p.kcopy ? h->eslot[p.slot].done : h->eslot[p.slot].staged));
-        const uint64_t n = h->ecount[p.slot];
+        GS_HIP(hipEventSynchronize(p.kcopy ? ea.done[p.slot].get() : ea.staged[p.slot].get()));
+        const uint64_t n = ea.ecount[p.slot];
         *p.n_out = n;
         if (n > p.cap) { over = n; over_cap = p.cap; continue; }
         if (n && !p.kcopy) {
             const hipMemcpyKind kind = hipMemcpyDeviceToHost;      // pageable host buffers
-            char* sv = static_cast<char*>(h->eslot[p.slot].mem) + 16;       // past the size word
+            char* sv = static_cast<char*>(h->eslot[p.slot].get()) + 16;       // past the size word
             const uint64_t scap = std::min<uint64_t>(p.cap, h->cap);
-            GS_HIP(hipMemcpyAsync(p.vertices, sv, n * esz, kind, h->estream));
-            GS_HIP(hipMemcpyAsync(p.labels, sv + scap * esz, n * esz, kind, h->estream));
-            GS_HIP(hipStreamSynchronize(h->estream));
+            GS_HIP(hipMemcpyAsync(p.vertices, sv, n * esz, kind, ea.estream));
+            GS_HIP(hipMemcpyAsync(p.labels, sv + scap * esz, n * esz, kind, ea.estream));
+            GS_HIP(hipStreamSynchronize(ea.estream));
         }
     }
     if (over) return fail(GS_ERR_CAPACITY, "gs_cc_emit_delta_async: %llu changed pairs, capacity %llu (nothing consumed)",
@@ -1814,9 +1723,9 @@ int gs_cc_find_flags(gs_cc_t* h, const void* ids, void* roots, uint8_t* found, u
     const void* di = ids;
     void* dr = roots;
     if (!dev) {
-        GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, 2 * n * esz));
+        GS_TRY(grow_tmp(h, 2 * n * esz));
         di = h->tmp;
-        dr = static_cast<char*>(h->tmp) + n * esz;
+        dr = static_cast<char*>(h->tmp.get()) + n * esz;
         GS_HIP(hipMemcpyAsync(const_cast<void*>(di), ids, n * esz, is_device_pointer(ids) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     }
     const dim3 grid(grid_for(n, 256, 16384));
@@ -1860,10 +1769,10 @@ int gsgpu::export_launch(gs_cc_t* h, void* out, uint64_t cap, unsigned long long
         KTimer t(h, GS_K_EXPORT);
         if (h->sparse)                               // (id, root id) as int64 pairs
             klaunch(k_export_log_sparse, dim3(grid), dim3(256), h->stream, t.start(), t.stop(), (const uint32_t*)h->mark_buf,
-                    h->mark_ctr, (const uint32_t*)h->parent, sparse_args(h), (int64_t*)out, cap, counter);
+                    h->mark_ctr.get(), (const uint32_t*)h->parent, sparse_args(h), (int64_t*)out, cap, counter);
         else
             klaunch(k_export_log, dim3(grid), dim3(256), h->stream, t.start(), t.stop(), (const uint32_t*)h->mark_buf,
-                    h->mark_ctr, (const uint32_t*)h->parent, (uint32_t*)out, cap, counter);
+                    h->mark_ctr.get(), (const uint32_t*)h->parent, (uint32_t*)out, cap, counter);
     }
     GS_HIP(hipGetLastError());
     return GS_OK;
@@ -1886,7 +1795,7 @@ int gs_cc_export_marks(gs_cc_t* h, void* pairs, uint64_t cap, uint64_t* n_out) {
     const bool dev = cap == 0 || is_device_pointer(pairs);
     void* out = pairs;
     if (!dev) {
-        GS_TRY(ensure_buf(&h->tmp, &h->tmp_bytes, cap * pair_bytes(h)));
+        GS_TRY(grow_tmp(h, cap * pair_bytes(h)));
         out = h->tmp;
     }
     GS_TRY(export_launch(h, out, cap, h->dscratch));
@@ -1923,9 +1832,9 @@ int gs_cc_filter_edges(gs_cc_t* h, const void* src, const void* dst, uint64_t n,
     if (n && !is_device_pointer(pairs)) return fail(GS_ERR_INVALID, "gs_cc_filter_edges: pairs must be device memory");
     *n_out = 0;
     DeviceGuard g(h->device);
-    unsigned long long* dcount = reinterpret_cast<unsigned long long*>(h->dscratch);
+    unsigned long long* dcount = h->dscratch;
     GS_TRY(cc_filter_async(h, src, dst, n, pairs, cap, dcount));
-    uint64_t* hc = reinterpret_cast<uint64_t*>(h->hscratch + 5);
+    uint64_t* hc = reinterpret_cast<uint64_t*>(h->hscratch + kHostFilterCount);
     GS_HIP(hipMemcpyAsync(hc, dcount, sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     GS_TRY(sync_and_check(h));
     *n_out = *hc;

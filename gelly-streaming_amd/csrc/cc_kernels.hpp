@@ -1516,8 +1516,8 @@ __global__ __launch_bounds__(256) void k_fold_slots(const uint32_t* __restrict__
     }
 }
 
-// Giant-component state (gs_cc_t::derr, cc_api.hip giant_state()): two slots of two words,
-// double-buffered by close parity, plus the hot set's owner:
+// Giant-component state (words of the control block gs_cc_t::derr; cc_api.hip enum Ctl gives the
+// whole layout): two slots of two words, double-buffered by close parity, plus the hot set's owner:
 //   slot[0] giant: the root the next close builds gbits for (followed to its current root first);
 //         kInvalid = none (no filter). The folds read the current slot's word: != kInvalid turns
 //         the filter on.

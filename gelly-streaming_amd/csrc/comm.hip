@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "cc_internal.hpp"
+#include "owned.hpp"
 
 namespace gsgpu {
 
@@ -101,46 +102,53 @@ struct gs_comm {
     int rank = 0, world = 1, device = 0;
     ncclComm_t nccl = nullptr;                     // RCCL transport
     std::shared_ptr<LocalGroup> local;             // or the in-process group
-    hipEvent_t ev_ready = nullptr, ev_done = nullptr;
+    Stream side;                                   // copies the slots' count words to the host
+    Event ev_ready, ev_done;
     // exchange buffers (device), sized at the first merge for the handle's capacity
     uint64_t cap_pairs = 0;
     uint64_t pair_bytes = 0;                       // 8: dense (uint32 vertex, root); 16: sparse (int64 ids)
-    uint32_t* sendbuf = nullptr;                   // cap_pairs pairs (2 x the handle's capacity)
+    DevBuf<uint32_t> sendbuf;                      // cap_pairs pairs (2 x the handle's capacity)
     uint64_t send_pairs = 0;                       // pairs each send buffer holds (count word included):
                                                    // cap_pairs + 1, more for a prefilter sender's big slice
-    uint32_t* sendbuf2 = nullptr;                  // allgather: exports alternate between the two, so a
+    DevBuf<uint32_t> sendbuf2;                     // allgather: exports alternate between the two, so a
                                                    // pending window's tail survives the next export
-    uint32_t* recvbuf = nullptr;                   // exact rounds: grows to world * m pairs
-    size_t recv_bytes = 0;
-    uint32_t* slotbuf = nullptr;                   // speculative rounds: world count-headed slots
-    size_t slot_bytes = 0;
-    unsigned long long* dcnt = nullptr;            // [world + 1]: all-gathered counts, [world] own/received
-    unsigned long long* hcnt = nullptr;            // pinned mirror
+    DevBuf<uint32_t> recvbuf;                      // exact rounds: grows to world * m pairs
+    DevBuf<uint32_t> slotbuf;                      // speculative rounds: world count-headed slots
+    DevBuf<unsigned long long> dcnt;               // [world + 1]: all-gathered counts, [world] own/received
+    Pinned<unsigned long long> hcnt;               // pinned mirror
     bool root_marking_off = false;
     uint64_t spec_slot = 0;                        // allgather: slot size of the speculative round (0: exact)
     gs_cc_t* bound = nullptr;                      // the one handle and mode this communicator serves
     int mode = -1;
     uint64_t reset_gen = 0;                        // the handle's reset generation of the current stream
     bool broken = false;                           // an exchange failed: the communicator is unusable
-    hipEvent_t ev_counts = nullptr;                // the speculative round's counts are on the host
-    hipEvent_t ev_slots = nullptr;                 // the speculative round's slots have arrived
-    hipStream_t side = nullptr;                    // copies the slots' count words to the host
+    Event ev_counts;                               // the speculative round's counts are on the host
+    Event ev_slots;                                // the speculative round's slots have arrived
     bool pending = false;                          // a speculative window not yet verified (settle_allgather)
     uint64_t pend_slot = 0;                        // its slot size S
     uint32_t* pend_buf = nullptr;                  // its export (the tail pairs [S, n) are sent from it)
     uint64_t last_delta = 0;                       // the largest delta of the last verified window
     std::vector<uint64_t> gslot;                   // gather: every sender's speculative slot (empty: exact round next)
     uint64_t win = 0;                              // prefilter: windows since the stream's start (broadcast schedule)
-    uint32_t* bword = nullptr;                     // prefilter: the broadcast giant slot words (device, 2)
+    DevBuf<uint32_t> bword;                        // prefilter: the broadcast giant slot words (device, 2)
     // prefilter, asynchronous filter-state broadcasts (after the first kBcastSync closes): their own
     // communicator (RCCL: split from the main one at bind; in-process: the same group) and stream
     ncclComm_t nccl_side = nullptr;
-    hipStream_t bside = nullptr;
-    uint32_t* bstage = nullptr;                    // rank 0: a snapshot [gbits | 2 giant words]; senders: 2 slots
-    uint64_t bslot_words = 0;                      // 32-bit words per slot
-    hipEvent_t ev_bmain = nullptr;                 // senders: a slot is free (its install ran); rank 0: the
+    struct Bcast {                                 // made on the first asynchronous broadcast
+        Stream bside;
+        DevBuf<uint32_t> bstage;                   // rank 0: a snapshot [gbits | 2 giant words]; senders: 2 slots
+        Event ev_bmain;                            // senders: a slot is free (its install ran); rank 0: the
                                                    // last broadcast has read the snapshot
-    hipEvent_t ev_brecv[2] = {nullptr, nullptr};   // senders: slot k has arrived; rank 0 ([0]): snapshot taken
+        Event ev_brecv[2];                         // senders: slot k has arrived; rank 0 ([0]): snapshot taken
+        int create(size_t words) {
+            GS_TRY(bside.create());
+            GS_TRY(ev_bmain.create());
+            GS_TRY(ev_brecv[0].create());
+            GS_TRY(ev_brecv[1].create());
+            return bstage.grow(words, "filter-state broadcast staging");
+        }
+    } bc;
+    uint64_t bslot_words = 0;                      // 32-bit words per slot
     int64_t bpend[2] = {-1, -1};                   // senders: the window whose state slot k holds (-1: none)
     uint64_t bytes_sent = 0, bytes_recv = 0, exchanges = 0, overflows = 0;
 };
@@ -263,21 +271,10 @@ struct Group {                                     // ncclGroupStart/End around 
     ~Group() { if (c && c->nccl) (void)ncclGroupEnd(); }
 };
 
-// Grows a device buffer. Folds already enqueued on the stream may still read the old one (a
-// receive buffer is read by the fold kernels that follow its collective), so the stream drains
-// before the free.
-int ensure(void** p, size_t* have, size_t need, hipStream_t s) {
-    if (*have >= need) return GS_OK;
-    if (*p) {
-        GS_HIP(hipStreamSynchronize(s));
-        GS_HIP(hipFree(*p));
-        *p = nullptr;
-        *have = 0;
-    }
-    if (hipMalloc(p, need) != hipSuccess) { (void)hipGetLastError(); return fail(GS_ERR_NOMEM, "hipMalloc(%zu) failed", need); }
-    *have = need;
-    return GS_OK;
-}
+// Grows a receive or slot buffer to `bytes`. Folds already enqueued on the stream may still read
+// the old one (a receive buffer is read by the fold kernels that follow its collective), so the
+// stream drains before the free.
+int ensure(DevBuf<uint32_t>& b, size_t bytes, hipStream_t s) { return b.grow((bytes + 3) / 4, "exchange buffer", s); }
 
 int prepare(gs_comm_t* c, gs_cc_t* h, CcInfo* info, int mode) {
     GS_TRY(cc_info(h, info));
@@ -289,14 +286,10 @@ int prepare(gs_comm_t* c, gs_cc_t* h, CcInfo* info, int mode) {
                                                info->device, c->device);
     const uint64_t need = 2ull * info->cap;        // an export never exceeds 2 x capacity pairs
     if (c->cap_pairs < need || c->pair_bytes != pbytes(*info)) {
-        if (c->sendbuf) (void)hipFree(c->sendbuf);
-        if (c->sendbuf2) (void)hipFree(c->sendbuf2);
-        c->sendbuf = c->sendbuf2 = nullptr;
-        if (hipMalloc(&c->sendbuf, (size_t)(need + 1) * pbytes(*info)) != hipSuccess ||      // + a count word
-            hipMalloc(&c->sendbuf2, (size_t)(need + 1) * pbytes(*info)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->cap_pairs = 0;
-            return fail(GS_ERR_NOMEM, "exchange buffers of %llu pairs", (unsigned long long)need);
+        c->cap_pairs = 0;
+        for (auto* b : {&c->sendbuf, &c->sendbuf2}) {
+            b->reset();                            // (a new pair size: new buffers even where the old would do)
+            GS_TRY(b->grow((size_t)(need + 1) * pbytes(*info) / 4, "exchange buffers"));      // + a count word
         }
         c->cap_pairs = need;
         c->send_pairs = need + 1;
@@ -310,17 +303,11 @@ int prepare(gs_comm_t* c, gs_cc_t* h, CcInfo* info, int mode) {
 // window was settled before merge_prefilter), so the old buffers are free once the stream drains.
 int ensure_send(gs_comm_t* c, uint64_t m, hipStream_t s) {
     if (m + 1 <= c->send_pairs) return GS_OK;
-    GS_HIP(hipStreamSynchronize(s));
-    if (c->sendbuf) (void)hipFree(c->sendbuf);
-    if (c->sendbuf2) (void)hipFree(c->sendbuf2);
-    c->sendbuf = c->sendbuf2 = nullptr;
     c->pend_buf = nullptr;
     c->send_pairs = 0;
     const uint64_t want = std::max<uint64_t>(m + 1, c->cap_pairs + 1);
-    if (hipMalloc(&c->sendbuf, (size_t)want * 8) != hipSuccess || hipMalloc(&c->sendbuf2, (size_t)want * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(GS_ERR_NOMEM, "prefilter send buffers of %llu pairs", (unsigned long long)want);
-    }
+    GS_TRY(c->sendbuf.grow((size_t)want * 2, "prefilter send buffers", s));
+    GS_TRY(c->sendbuf2.grow((size_t)want * 2, "prefilter send buffers", s));
     c->send_pairs = want;
     return GS_OK;
 }
@@ -372,7 +359,7 @@ int exchange_exact(gs_comm_t* c, gs_cc_t* h, const CcInfo& in, uint64_t* maxc) {
         const uint64_t n = cnt[c->rank];
         if (n && n < m) pad_pairs(in.sparse, c->sendbuf, n, m, s);
         GS_HIP(hipGetLastError());
-        GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)P * m * pbytes(in), s));
+        GS_TRY(ensure(c->recvbuf, (size_t)P * m * pbytes(in), s));
         GS_TRY(allgather(c, c->sendbuf, c->recvbuf, m * pbytes(in), s));
         std::vector<char> skip(P, 0);
         skip[c->rank] = 1;
@@ -441,7 +428,7 @@ int settle_allgather(gs_comm_t* c, bool close) {
         const uint64_t n = tail[c->rank];
         if (n && n < mt) pad_pairs(in.sparse, t, n, mt, s);
         GS_HIP(hipGetLastError());
-        GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)P * mt * pbytes(in), s));
+        GS_TRY(ensure(c->recvbuf, (size_t)P * mt * pbytes(in), s));
         GS_TRY(allgather(c, t, c->recvbuf, mt * pbytes(in), s));
         std::vector<char> skip(P, 0);
         skip[c->rank] = 1;
@@ -502,7 +489,7 @@ int merge_allgather(gs_comm_t* c, gs_cc_t* h, const CcInfo& in) {
     }
     const uint64_t S = c->spec_slot;
     const uint64_t slot_words = 2 + pwords(in) * S;              // [u64 count][S pairs]
-    GS_TRY(ensure(reinterpret_cast<void**>(&c->slotbuf), &c->slot_bytes, (size_t)P * slot_words * 4, s));
+    GS_TRY(ensure(c->slotbuf, (size_t)P * slot_words * 4, s));
     GS_TRY(allgather(c, send, c->slotbuf, slot_words * 4, s));
     // the count words (one per slot, strided) go to the host on a side stream, so the slots' fold
     // and the close start right after the collective; settle_allgather reads them (the next
@@ -563,7 +550,7 @@ int merge_gather_exact(gs_comm_t* c, gs_cc_t* h, const CcInfo& in) {
         c->gslot[q] = next_slot(c, cnt[q]);
     }
     if (total) {
-        GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)total * pbytes(in), s));
+        GS_TRY(ensure(c->recvbuf, (size_t)total * pbytes(in), s));
         {
             Group g(c);
             uint64_t off = 0;
@@ -633,7 +620,7 @@ int settle_gather(gs_comm_t* c, bool close) {
     c->last_delta = mx;
     if (total) {
         ++c->overflows;
-        GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)total * pbytes(in), s));
+        GS_TRY(ensure(c->recvbuf, (size_t)total * pbytes(in), s));
         {
             Group gr(c);
             uint64_t off = 0;
@@ -679,7 +666,7 @@ int merge_gather(gs_comm_t* c, gs_cc_t* h, const CcInfo& in) {
     uint64_t smax = 0;
     for (int q = 1; q < P; ++q) smax = std::max(smax, c->gslot[q]);
     const uint64_t slot_words = 2 + pwords(in) * smax;
-    GS_TRY(ensure(reinterpret_cast<void**>(&c->slotbuf), &c->slot_bytes, (size_t)P * slot_words * 4, s));
+    GS_TRY(ensure(c->slotbuf, (size_t)P * slot_words * 4, s));
     {
         Group g(c);
         for (int q = 1; q < P; ++q)
@@ -739,17 +726,8 @@ bool bcast_async(uint64_t win) {
 
 // side stream, events and staging of the asynchronous broadcasts (first use)
 int bside_init(gs_comm_t* c, uint64_t slot_words) {
-    if (c->bstage) return GS_OK;                     // (the last piece: everything before it exists)
-    // a failed attempt keeps what it created (gs_comm_destroy frees it) and the next one goes on
-    if ((!c->bside && hipStreamCreateWithFlags(&c->bside, hipStreamNonBlocking) != hipSuccess) ||
-        (!c->ev_bmain && hipEventCreateWithFlags(&c->ev_bmain, hipEventDisableTiming) != hipSuccess) ||
-        (!c->ev_brecv[0] && hipEventCreateWithFlags(&c->ev_brecv[0], hipEventDisableTiming) != hipSuccess) ||
-        (!c->ev_brecv[1] && hipEventCreateWithFlags(&c->ev_brecv[1], hipEventDisableTiming) != hipSuccess) ||
-        hipMalloc(&c->bstage, (size_t)slot_words * 4 * (c->rank == 0 ? 1 : 2)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->bstage = nullptr;
-        return fail(GS_ERR_NOMEM, "prefilter broadcast staging");
-    }
+    if (c->bc.bstage) return GS_OK;
+    GS_TRY(make_whole(c->bc, (size_t)slot_words * (c->rank == 0 ? 1 : 2)));
     c->bslot_words = slot_words;
     c->bpend[0] = c->bpend[1] = -1;
     return GS_OK;
@@ -765,13 +743,13 @@ int bcast_async_send(gs_comm_t* c, gs_cc_t* h, hipStream_t s) {
     // could overlap the next close, and a giant switch there (the bitmap rebuilt for another
     // component) would mix two components' bits (8 MiB at 2^26 ids: a few us). The previous
     // broadcast must have read the buffer first.
-    GS_HIP(hipStreamWaitEvent(s, c->ev_bmain, 0));
-    GS_HIP(hipMemcpyAsync(c->bstage, gb, gbytes, hipMemcpyDeviceToDevice, s));
-    GS_HIP(hipMemcpyAsync(c->bstage + gbytes / 4, words, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    GS_HIP(hipEventRecord(c->ev_brecv[0], s));                  // the snapshot is complete
-    GS_HIP(hipStreamWaitEvent(c->bside, c->ev_brecv[0], 0));
-    GS_TRY(bcast(c, c->bstage, gbytes + 8, c->bside, true));
-    GS_HIP(hipEventRecord(c->ev_bmain, c->bside));              // the buffer may be rewritten after this
+    GS_HIP(hipStreamWaitEvent(s, c->bc.ev_bmain, 0));
+    GS_HIP(hipMemcpyAsync(c->bc.bstage, gb, gbytes, hipMemcpyDeviceToDevice, s));
+    GS_HIP(hipMemcpyAsync(c->bc.bstage + gbytes / 4, words, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    GS_HIP(hipEventRecord(c->bc.ev_brecv[0], s));                  // the snapshot is complete
+    GS_HIP(hipStreamWaitEvent(c->bc.bside, c->bc.ev_brecv[0], 0));
+    GS_TRY(bcast(c, c->bc.bstage, gbytes + 8, c->bc.bside, true));
+    GS_HIP(hipEventRecord(c->bc.ev_bmain, c->bc.bside));              // the buffer may be rewritten after this
     c->bytes_sent += (gbytes + 8) * (c->world - 1);
     return GS_OK;
 }
@@ -784,9 +762,9 @@ int bcast_async_recv(gs_comm_t* c, gs_cc_t* h, uint64_t win) {
     GS_TRY(bside_init(c, gbytes / 4 + 2));
     const int k = (int)(win & 1);
     // (the slot's last install was recorded in ev_bmain, which the side stream waits for)
-    GS_HIP(hipStreamWaitEvent(c->bside, c->ev_bmain, 0));
-    GS_TRY(bcast(c, c->bstage + (size_t)k * c->bslot_words, gbytes + 8, c->bside, true));
-    GS_HIP(hipEventRecord(c->ev_brecv[k], c->bside));
+    GS_HIP(hipStreamWaitEvent(c->bc.bside, c->bc.ev_bmain, 0));
+    GS_TRY(bcast(c, c->bc.bstage + (size_t)k * c->bslot_words, gbytes + 8, c->bc.bside, true));
+    GS_HIP(hipEventRecord(c->bc.ev_brecv[k], c->bc.bside));
     c->bpend[k] = (int64_t)win;
     c->bytes_recv += gbytes + 8;
     return GS_OK;
@@ -801,11 +779,11 @@ int bcast_async_install(gs_comm_t* c, gs_cc_t* h, uint64_t win, hipStream_t s) {
     uint32_t *gb = nullptr, *words = nullptr;
     uint64_t gbytes = 0;
     GS_TRY(cc_filter_state(h, &gb, &gbytes, &words));
-    const uint32_t* slot = c->bstage + (size_t)k * c->bslot_words;
-    GS_HIP(hipStreamWaitEvent(s, c->ev_brecv[k], 0));
+    const uint32_t* slot = c->bc.bstage + (size_t)k * c->bslot_words;
+    GS_HIP(hipStreamWaitEvent(s, c->bc.ev_brecv[k], 0));
     GS_HIP(hipMemcpyAsync(gb, slot, gbytes, hipMemcpyDeviceToDevice, s));
     GS_TRY(cc_install_giant(h, slot + gbytes / 4));
-    GS_HIP(hipEventRecord(c->ev_bmain, s));                      // slot k free for the next receive
+    GS_HIP(hipEventRecord(c->bc.ev_bmain, s));                      // slot k free for the next receive
     c->bpend[k] = -1;
     return GS_OK;
 }
@@ -814,12 +792,7 @@ int bcast_filter_state(gs_comm_t* c, gs_cc_t* h, hipStream_t s) {
     uint32_t *gb = nullptr, *words = nullptr;
     uint64_t gbytes = 0;
     GS_TRY(cc_filter_state(h, &gb, &gbytes, &words));
-    if (!c->bword) {
-        if (hipMalloc(&c->bword, 2 * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(GS_ERR_NOMEM, "broadcast words");
-        }
-    }
+    GS_TRY(c->bword.grow(2, "broadcast words"));
     if (c->rank == 0) GS_HIP(hipMemcpyAsync(c->bword, words, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     {
         Group g(c);
@@ -843,7 +816,7 @@ int merge_prefilter(gs_comm_t* c, gs_cc_t* h, const CcInfo& in, const void* a, c
         GS_TRY(ensure_send(c, m, s));
         GS_TRY(bcast_async_install(c, h, win, s));
         if (exact) {
-            GS_TRY(cc_filter_async(h, a, b, m, c->sendbuf + 2, c->send_pairs - 1, reinterpret_cast<unsigned long long*>(c->sendbuf)));
+            GS_TRY(cc_filter_async(h, a, b, m, c->sendbuf + 2, c->send_pairs - 1, reinterpret_cast<unsigned long long*>(c->sendbuf.get())));
             GS_HIP(hipMemcpyAsync(c->hcnt + P, c->sendbuf, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
             GS_HIP(hipStreamSynchronize(s));
             const uint64_t n = c->hcnt[P];
@@ -894,7 +867,7 @@ int merge_prefilter(gs_comm_t* c, gs_cc_t* h, const CcInfo& in, const void* a, c
             c->gslot[q] = next_slot(c, cnt[q]);
         }
         if (total) {
-            GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)total * 8, s));
+            GS_TRY(ensure(c->recvbuf, (size_t)total * 8, s));
             {
                 Group g(c);
                 uint64_t off = 0;
@@ -915,7 +888,7 @@ int merge_prefilter(gs_comm_t* c, gs_cc_t* h, const CcInfo& in, const void* a, c
         uint64_t smax = 0;
         for (int q = 1; q < P; ++q) smax = std::max(smax, c->gslot[q]);
         const uint64_t slot_words = 2 + 2 * smax;
-        GS_TRY(ensure(reinterpret_cast<void**>(&c->slotbuf), &c->slot_bytes, (size_t)P * slot_words * 4, s));
+        GS_TRY(ensure(c->slotbuf, (size_t)P * slot_words * 4, s));
         {
             Group g(c);
             for (int q = 1; q < P; ++q)
@@ -967,7 +940,7 @@ int merge_tree(gs_comm_t* c, gs_cc_t* h, const CcInfo& in) {
             GS_HIP(hipStreamSynchronize(s));
             const uint64_t n = c->hcnt[0];
             if (n) {
-                GS_TRY(ensure(reinterpret_cast<void**>(&c->recvbuf), &c->recv_bytes, (size_t)n * pbytes(in), s));
+                GS_TRY(ensure(c->recvbuf, (size_t)n * pbytes(in), s));
                 GS_TRY(recv(c, c->recvbuf, n * pbytes(in), peer, s));
                 GS_TRY(cc_fold_pairs_any(h, c->recvbuf, n));
             }
@@ -978,16 +951,10 @@ int merge_tree(gs_comm_t* c, gs_cc_t* h, const CcInfo& in) {
 }
 
 int alloc_common(gs_comm_t* c) {
-    if (hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_counts, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_slots, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->dcnt, (c->world + 1) * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(&c->hcnt, (c->world + 1) * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(GS_ERR_NOMEM, "communicator scratch allocation failed");
-    }
+    for (Event* e : {&c->ev_ready, &c->ev_counts, &c->ev_done, &c->ev_slots}) GS_TRY(e->create());
+    GS_TRY(c->side.create());
+    GS_TRY(c->dcnt.grow(c->world + 1, "communicator scratch"));
+    GS_TRY(c->hcnt.alloc(c->world + 1, "communicator scratch"));
     GS_HIP(hipMemset(c->dcnt, 0, (c->world + 1) * sizeof(unsigned long long)));
     return GS_OK;
 }
@@ -1060,24 +1027,7 @@ int gs_comm_destroy(gs_comm_t* c) {
     (void)hipDeviceSynchronize();
     if (c->nccl_side) (void)ncclCommDestroy(c->nccl_side);
     if (c->nccl) (void)ncclCommDestroy(c->nccl);
-    if (c->bside) (void)hipStreamDestroy(c->bside);
-    if (c->ev_bmain) (void)hipEventDestroy(c->ev_bmain);
-    for (hipEvent_t e : c->ev_brecv)
-        if (e) (void)hipEventDestroy(e);
-    if (c->bstage) (void)hipFree(c->bstage);
-    if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
-    if (c->ev_done) (void)hipEventDestroy(c->ev_done);
-    if (c->ev_counts) (void)hipEventDestroy(c->ev_counts);
-    if (c->ev_slots) (void)hipEventDestroy(c->ev_slots);
-    if (c->side) (void)hipStreamDestroy(c->side);
-    if (c->sendbuf) (void)hipFree(c->sendbuf);
-    if (c->sendbuf2) (void)hipFree(c->sendbuf2);
-    if (c->recvbuf) (void)hipFree(c->recvbuf);
-    if (c->slotbuf) (void)hipFree(c->slotbuf);
-    if (c->bword) (void)hipFree(c->bword);
-    if (c->dcnt) (void)hipFree(c->dcnt);
-    if (c->hcnt) (void)hipHostFree(c->hcnt);
-    delete c;
+    delete c;                                       // the owners free what it holds (owned.hpp)
     return GS_OK;
 }
 

@@ -15,8 +15,21 @@ namespace gsgpu {
 constexpr uint32_t kInvalid = 0xFFFFFFFFu;   // parent[v] of a vertex not in the summary
 constexpr int kMaxSlotCaps = 16;              // slots of a fold with per-slot capacities (SlotCaps)
 
-std::string& last_error();
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// the calling thread's last error message (gs_last_error) and the one way to set it
+inline std::string& last_error() {
+    static thread_local std::string s;
+    return s;
+}
+
+__attribute__((format(printf, 2, 3))) inline int fail(int code, const char* fmt, ...) {
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    last_error() = buf;
+    return code;
+}
 
 #define GS_HIP(expr)                                                                         \
     do {                                                                                     \

@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cerrno>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -27,6 +28,7 @@
 #include <unistd.h>
 
 #include "cc_internal.hpp"
+#include "owned.hpp"
 
 namespace gsgpu {
 
@@ -320,60 +322,24 @@ using namespace gsgpu;
 namespace {
 
 // Device scratch of one parse: chunk '\n' counts, their offsets, per-1024-chunk group sums and
-// prefixes, the bad-line word, and a pinned mirror [bad line, '\n' count, last byte]. Every buffer
-// records its own capacity and a failed allocation leaves it empty (capacity 0), so a later call
-// allocates again instead of launching on a null pointer.
-template <typename T>
-int grow_elems(T** p, size_t* cap, size_t want, const char* what) {
-    if (*p && *cap >= want) return GS_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(p), want * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(GS_ERR_NOMEM, "%s: %zu bytes of scratch", what, want * sizeof(T));
-    }
-    *cap = want;
-    return GS_OK;
-}
-
+// prefixes, the bad-line word, and a pinned mirror [bad line, '\n' count, last byte]. A failed
+// allocation leaves its buffer empty (owned.hpp), so a later call allocates again instead of
+// launching on a null pointer.
 struct ParseScratch {
-    uint32_t* cnt = nullptr;
-    size_t cnt_cap = 0;
-    uint64_t* off = nullptr;
-    size_t off_cap = 0;
-    unsigned long long* gsum = nullptr;
-    size_t gsum_cap = 0;
-    unsigned long long* gpre = nullptr;
-    size_t gpre_cap = 0;
-    unsigned long long* bad = nullptr;
-    size_t bad_cap = 0;
-    unsigned long long* hbuf = nullptr;   // pinned: [bad line, '\n' count, last byte of the text]
+    DevBuf<uint32_t> cnt;
+    DevBuf<uint64_t> off;
+    DevBuf<unsigned long long> gsum, gpre, bad;
+    Pinned<unsigned long long> hbuf;      // [bad line, '\n' count, last byte of the text]
 
     int ensure(uint32_t nb, const char* what) {
         const uint32_t ng = (nb + kScanGroup - 1) / kScanGroup;
-        GS_TRY(grow_elems(&cnt, &cnt_cap, (size_t)nb + 1, what));
-        GS_TRY(grow_elems(&off, &off_cap, (size_t)nb + 2, what));
-        GS_TRY(grow_elems(&gsum, &gsum_cap, (size_t)std::max<uint32_t>(ng, 1), what));
-        GS_TRY(grow_elems(&gpre, &gpre_cap, (size_t)std::max<uint32_t>(ng, 1), what));
-        GS_TRY(grow_elems(&bad, &bad_cap, 1, what));
-        if (!hbuf) {
-            if (hipHostMalloc(reinterpret_cast<void**>(&hbuf), 3 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                hbuf = nullptr;
-                return fail(GS_ERR_NOMEM, "%s: pinned scratch", what);
-            }
-        }
+        GS_TRY(cnt.grow((size_t)nb + 1, what));
+        GS_TRY(off.grow((size_t)nb + 2, what));
+        GS_TRY(gsum.grow((size_t)std::max<uint32_t>(ng, 1), what));
+        GS_TRY(gpre.grow((size_t)std::max<uint32_t>(ng, 1), what));
+        GS_TRY(bad.grow(1, what));
+        if (!hbuf) GS_TRY(hbuf.alloc(3, what));
         return GS_OK;
-    }
-    void release() {
-        if (cnt) (void)hipFree(cnt);
-        if (off) (void)hipFree(off);
-        if (gsum) (void)hipFree(gsum);
-        if (gpre) (void)hipFree(gpre);
-        if (bad) (void)hipFree(bad);
-        if (hbuf) (void)hipHostFree(hbuf);
-        *this = ParseScratch{};
     }
 };
 
@@ -417,13 +383,8 @@ constexpr int kMaxParseDevices = 64;
 constexpr size_t kKeepText = 256ull << 20;
 struct ParseDevice {
     std::mutex mu;
-    ParseScratch sc;
-    char* text = nullptr;
-    size_t text_cap = 0;
-    ~ParseDevice() {                       // (process exit: the runtime may already be gone; best effort)
-        if (text) (void)hipFree(text);
-        sc.release();
-    }
+    ParseScratch sc;                       // (freed at process exit, when the runtime may already be gone:
+    DevBuf<char> text;                     // best effort, the owners ignore errors)
 };
 ParseDevice g_parse[kMaxParseDevices];
 
@@ -436,7 +397,7 @@ int parse_edges_locked(ParseDevice& pd, const char* text, uint64_t n_bytes, uint
     // the kernels read the text in 16-B loads: host or misaligned device text goes through a copy
     const char* dtext = text;
     if (!is_device_pointer(text) || (reinterpret_cast<uintptr_t>(text) & 15)) {
-        GS_TRY(grow_elems(&pd.text, &pd.text_cap, n_bytes, "gs_parse_edges"));
+        GS_TRY(pd.text.grow(n_bytes, "gs_parse_edges"));
         GS_HIP(hipMemcpyAsync(pd.text, text, n_bytes, hipMemcpyDefault, s));
         dtext = pd.text;
     }
@@ -452,14 +413,12 @@ int parse_edges_locked(ParseDevice& pd, const char* text, uint64_t n_bytes, uint
     const bool dev_out = is_device_pointer(src) && is_device_pointer(dst);
     void* dsrc = src;
     void* ddst = dst;
-    if (!dev_out) {                                          // host outputs: staged per call
-        dsrc = ddst = nullptr;
-        if (hipMalloc(&dsrc, (size_t)std::max<uint64_t>(lines, 1) * esz) != hipSuccess ||
-            hipMalloc(&ddst, (size_t)std::max<uint64_t>(lines, 1) * esz) != hipSuccess) {
-            (void)hipGetLastError();
-            if (dsrc) (void)hipFree(dsrc);
-            return fail(GS_ERR_NOMEM, "gs_parse_edges: output staging");
-        }
+    DevBuf<> ssrc, sdst;                                     // host outputs: staged per call
+    if (!dev_out) {
+        GS_TRY(ssrc.grow((size_t)std::max<uint64_t>(lines, 1) * esz, "gs_parse_edges: output staging"));
+        GS_TRY(sdst.grow((size_t)std::max<uint64_t>(lines, 1) * esz, "gs_parse_edges: output staging"));
+        dsrc = ssrc;
+        ddst = sdst;
     }
     LineOut lo;
     lo.lcap = lines;
@@ -469,10 +428,6 @@ int parse_edges_locked(ParseDevice& pd, const char* text, uint64_t n_bytes, uint
          hipMemcpyAsync(dst, ddst, lines * esz, hipMemcpyDeviceToHost, s) != hipSuccess))
         rc = fail(GS_ERR_HIP, "gs_parse_edges: copy of the outputs failed");
     if (hipStreamSynchronize(s) != hipSuccess && rc == GS_OK) rc = fail(GS_ERR_HIP, "gs_parse_edges: stream sync failed");
-    if (!dev_out) {
-        (void)hipFree(dsrc);
-        (void)hipFree(ddst);
-    }
     if (rc != GS_OK) return rc;
     const unsigned long long first_bad = sc.hbuf[0];
     if (first_bad != ~0ull) {
@@ -499,11 +454,9 @@ extern "C" int gs_parse_edges(const char* text, uint64_t n_bytes, uint32_t id_bi
     ParseDevice& pd = g_parse[device];
     std::lock_guard<std::mutex> lock(pd.mu);
     const int rc = parse_edges_locked(pd, text, n_bytes, id_bits, src, dst, cap, n_edges, static_cast<hipStream_t>(stream));
-    if (pd.text && pd.text_cap > kKeepText) {
+    if (pd.text.capacity() > kKeepText) {
         (void)hipStreamSynchronize(static_cast<hipStream_t>(stream));
-        (void)hipFree(pd.text);
-        pd.text = nullptr;
-        pd.text_cap = 0;
+        pd.text.reset();
     }
     return rc;
 }
@@ -531,59 +484,53 @@ struct Ingest {
     int device = 0;
     uint32_t esz = 0;
     uint64_t chunk = 0, lmax = 0, ring = 0;
-    char* pin[2] = {nullptr, nullptr};    // pinned staging (file and pageable sources)
-    char* dtext[2] = {nullptr, nullptr};  // device text of chunks i & 1
-    void* rs = nullptr;                   // edge ring: src ids, dst ids (ring entries each)
-    void* rd = nullptr;
+    // the streams and events live as long as the handle ...
+    Stream cs, ps;
+    Event copied[2], counted[2], parsed[2], folded[2], start;
+    // ... the buffers are sized for one chunk and ring size (release() drops them when either changes)
+    Pinned<char> pin[2];                  // pinned staging (file and pageable sources)
+    DevBuf<char> dtext[2];                // device text of chunks i & 1
+    DevBuf<> rs, rd;                      // edge ring: src ids, dst ids (ring entries each)
     ParseScratch sc[2];
-    hipStream_t cs = nullptr, ps = nullptr;
-    hipEvent_t copied[2] = {}, counted[2] = {}, parsed[2] = {}, folded[2] = {}, start = nullptr;
 
-    void release() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        if (ps) (void)hipStreamSynchronize(ps);
-        for (int k = 0; k < 2; ++k) {
-            if (pin[k]) (void)hipHostFree(pin[k]);
-            if (dtext[k]) (void)hipFree(dtext[k]);
-            pin[k] = dtext[k] = nullptr;
-            sc[k].release();
-        }
-        if (rs) (void)hipFree(rs);
-        if (rd) (void)hipFree(rd);
-        rs = rd = nullptr;
-        chunk = ring = lmax = 0;
+    int create(int dev) {
+        device = dev;
+        GS_TRY(cs.create());
+        GS_TRY(ps.create());
+        for (Event* e : {&copied[0], &copied[1], &counted[0], &counted[1], &parsed[0], &parsed[1], &folded[0], &folded[1], &start})
+            GS_TRY(e->create());
+        return GS_OK;
     }
-    void destroy() {
-        release();
-        for (int k = 0; k < 2; ++k)
-            for (hipEvent_t* e : {&copied[k], &counted[k], &parsed[k], &folded[k]})
-                if (*e) (void)hipEventDestroy(*e);
-        if (start) (void)hipEventDestroy(start);
-        if (cs) (void)hipStreamDestroy(cs);
-        if (ps) (void)hipStreamDestroy(ps);
+    void release() {
+        (void)hipStreamSynchronize(cs);
+        (void)hipStreamSynchronize(ps);
+        for (int k = 0; k < 2; ++k) {
+            pin[k].reset();
+            dtext[k].reset();
+            sc[k] = ParseScratch{};
+        }
+        rs.reset();
+        rd.reset();
+        chunk = ring = lmax = 0;
     }
 };
 
 void ingest_free(void* p) {
     Ingest* g = static_cast<Ingest*>(p);
     DeviceGuard dg(g->device);
-    g->destroy();
+    g->release();                         // (its streams synchronised before anything is freed)
     delete g;
 }
 
-// the handle's ingestion state, sized for chunks of `chunk` bytes and windows of W edges
+// the handle's ingestion state, sized for chunks of `chunk` bytes and windows of W edges; installed
+// in the handle only once its streams and events all exist
 int ingest_get(gs_cc_t* h, const CcInfo& in, uint32_t id_bits, uint64_t chunk, uint64_t W, Ingest** out) {
     Ingest* g = static_cast<Ingest*>(cc_ingest_get(h));
     if (!g) {
-        g = new Ingest();
-        g->device = in.device;
+        std::unique_ptr<Ingest> made(new Ingest());
+        GS_TRY(made->create(in.device));
+        g = made.release();
         cc_ingest_set(h, g, ingest_free);
-        GS_HIP(hipStreamCreateWithFlags(&g->cs, hipStreamNonBlocking));
-        GS_HIP(hipStreamCreateWithFlags(&g->ps, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k)
-            for (hipEvent_t* e : {&g->copied[k], &g->counted[k], &g->parsed[k], &g->folded[k]})
-                GS_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        GS_HIP(hipEventCreateWithFlags(&g->start, hipEventDisableTiming));
     }
     const uint32_t esz = id_bits / 8;
     const uint64_t lmax = chunk / 4 + 1;
@@ -592,20 +539,14 @@ int ingest_get(gs_cc_t* h, const CcInfo& in, uint32_t id_bits, uint64_t chunk, u
     if (g->chunk < chunk || g->ring < ring || g->esz != esz || g->ring % W) {
         g->release();
         g->esz = esz;
+        // (a failure leaves chunk = ring = 0: the next call drops what exists and sizes again)
         for (int k = 0; k < 2; ++k) {
-            if (hipHostMalloc(reinterpret_cast<void**>(&g->pin[k]), chunk, hipHostMallocDefault) != hipSuccess ||
-                hipMalloc(&g->dtext[k], chunk) != hipSuccess) {
-                (void)hipGetLastError();
-                g->release();
-                return fail(GS_ERR_NOMEM, "gs_cc_fold_text: staging buffers of %llu bytes", (unsigned long long)chunk);
-            }
+            GS_TRY(g->pin[k].alloc(chunk, "gs_cc_fold_text: staging buffers"));
+            GS_TRY(g->dtext[k].grow(chunk, "gs_cc_fold_text: staging buffers"));
             GS_TRY(g->sc[k].ensure((uint32_t)((chunk + kChunk - 1) / kChunk), "gs_cc_fold_text"));
         }
-        if (hipMalloc(&g->rs, ring * esz) != hipSuccess || hipMalloc(&g->rd, ring * esz) != hipSuccess) {
-            (void)hipGetLastError();
-            g->release();
-            return fail(GS_ERR_NOMEM, "gs_cc_fold_text: edge ring of %llu edges", (unsigned long long)ring);
-        }
+        GS_TRY(g->rs.grow(ring * esz, "gs_cc_fold_text: edge ring"));
+        GS_TRY(g->rd.grow(ring * esz, "gs_cc_fold_text: edge ring"));
         g->chunk = chunk;
         g->ring = ring;
         g->lmax = lmax;
@@ -691,8 +632,8 @@ struct WindowHook {
     void* ctx = nullptr;
 };
 int fold_ring(gs_cc_t* h, Ingest* g, uint64_t G, uint64_t L, uint64_t W, uint64_t* windows, const WindowHook& hook) {
-    const char* rs = static_cast<const char*>(g->rs);
-    const char* rd = static_cast<const char*>(g->rd);
+    const char* rs = static_cast<const char*>(g->rs.get());
+    const char* rd = static_cast<const char*>(g->rd.get());
     const size_t esz = g->esz;
     while (L) {
         const uint64_t r = G % g->ring;                 // ring position (windows never wrap: R % W == 0)
