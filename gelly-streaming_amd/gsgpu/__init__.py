@@ -7,9 +7,10 @@ from .summary import DisjointSet, UpdateCC, CombineCC, combine_cc  # noqa: F401
 from .aggregation import (SimpleEdgeStream, SummaryBulkAggregation, ConnectedComponents,  # noqa: F401
                           SummaryTreeReduce, ConnectedComponentsTree)
 from .bipartite import Candidates, BipartitenessCheck  # noqa: F401
+from .triangles import TriangleCounter, WindowTriangles  # noqa: F401
 from .comm import Comm  # noqa: F401
 
 __all__ = ["DisjointSet", "UpdateCC", "CombineCC", "combine_cc", "SimpleEdgeStream",
            "SummaryBulkAggregation", "ConnectedComponents", "SummaryTreeReduce", "ConnectedComponentsTree",
-           "Candidates", "BipartitenessCheck", "GsError", "GsgpuUnavailable",
+           "Candidates", "BipartitenessCheck", "TriangleCounter", "WindowTriangles", "GsError", "GsgpuUnavailable",
            "available", "lib"]

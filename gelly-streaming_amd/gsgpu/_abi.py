@@ -26,6 +26,7 @@ GS_ERR_COMM = -8
 GS_CC_TRACK_MARKS = 1
 GS_CC_SPARSE_IDS = 2
 GS_BIP_REFERENCE_LITERAL = 1
+GS_TRI_ORIENT_BY_ID = 1
 
 GS_K_FOLD, GS_K_COMPRESS, GS_K_MERGE, GS_K_EXPORT, GS_K_RING = 0, 1, 2, 3, 4
 GS_MERGE_ALLGATHER, GS_MERGE_GATHER, GS_MERGE_TREE, GS_MERGE_PREFILTER = 0, 1, 2, 3
@@ -47,6 +48,8 @@ EXPORTED_SYMBOLS = (
     "gs_bip_create", "gs_bip_destroy", "gs_bip_reset", "gs_bip_set_stream", "gs_bip_sync", "gs_bip_fold",
     "gs_bip_fold_pairs", "gs_bip_merge", "gs_bip_close_window", "gs_bip_status", "gs_bip_checksum",
     "gs_bip_emit_pairs", "gs_bip_create_ex", "gs_bip_restore",
+    "gs_tri_create", "gs_tri_destroy", "gs_tri_set_stream", "gs_tri_get_stream", "gs_tri_sync",
+    "gs_tri_count_windows", "gs_tri_count_local",
     "gs_comm_unique_id", "gs_comm_create", "gs_comm_create_local", "gs_comm_destroy", "gs_comm_info",
     "gs_cc_merge_window", "gs_cc_fold_windows",
     "gs_last_error", "gs_version",
@@ -159,6 +162,13 @@ def lib() -> ctypes.CDLL:
         "gs_bip_checksum": [vp, P(u64), P(i32), P(u64), P(u64)],
         "gs_bip_emit_pairs": [vp, vp, vp, vp, u64, P(u64)],
         "gs_bip_restore": [vp, i32, vp, vp, vp, u64],
+        "gs_tri_create": [P(vp), u64, u32, i32, u32],
+        "gs_tri_destroy": [vp],
+        "gs_tri_set_stream": [vp, vp],
+        "gs_tri_get_stream": [vp, P(vp)],
+        "gs_tri_sync": [vp],
+        "gs_tri_count_windows": [vp, vp, vp, u64, u64, vp, u64, P(u64)],
+        "gs_tri_count_local": [vp, vp, vp, u64, vp, P(u64), P(u64)],
         "gs_comm_unique_id": [vp, u64],
         "gs_comm_create": [P(vp), vp, i32, i32, i32],
         "gs_comm_create_local": [P(vp), i32, i32],

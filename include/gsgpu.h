@@ -338,6 +338,38 @@ int gs_bip_checksum(gs_bip_t* h, uint64_t* checksum, int* bipartite, uint64_t* n
 int gs_bip_emit_pairs(gs_bip_t* h, void* vertices, void* keys, uint8_t* signs, uint64_t cap, uint64_t* n_out);
 int gs_bip_restore(gs_bip_t* h, int bipartite, const void* vertices, const void* keys, const uint8_t* signs, uint64_t n);
 
+/* ---- WindowTriangles (example/WindowTriangles.java:60-65, :82-139) ----
+ * Exact triangle counts of edge windows: slice(window, ALL) -> GenerateCandidateEdges ->
+ * CountTriangles -> timeWindowAll.sum. The count of a window is the number of triangles of its
+ * simple undirected graph: repeated edges and both directions count once, every triangle is found
+ * once (at its lowest vertex of the orientation). Self-loops are ignored (with one the reference's
+ * count depends on HashSet iteration order). Dense ids in [0, vertex_capacity), vertex_capacity
+ * <= 2^32, id_bits 32 or 64. A handle holds no summary between calls, only scratch memory.
+ *   flags: GS_TRI_ORIENT_BY_ID   orient edges low id -> high id (the reference's own rule, "IDs
+ *          larger than the vertex ID"); default low (degree, id) -> high (degree, id), under which
+ *          no out-row holds more than sqrt(2 m) of a window's m simple edges.
+ *   gs_tri_count_windows  every window of window_edges edges (the last may be shorter):
+ *          counts[w] = triangles of window w (host array of cap entries); *n_windows =
+ *          ceil(n / window_edges); cap < that: GS_ERR_CAPACITY, nothing counted. One host wait,
+ *          at the end. src/dst host or device, id_bits wide, as gs_cc_fold. n == 0: GS_OK,
+ *          *n_windows = 0.
+ *   gs_tri_count_local    one window; local (nullable, host or device, vertex_capacity uint64
+ *          entries) = triangles per vertex (for a stream without repeated edges: the final
+ *          per-vertex counters of ExactTriangleCount.java); *triangles = the total,
+ *          *simple_edges (nullable) = distinct undirected edges without self-loops.
+ * An id outside [0, vertex_capacity): GS_ERR_RANGE, and the call reports no count. */
+typedef struct gs_tri gs_tri_t;
+enum { GS_TRI_ORIENT_BY_ID = 1 };
+int gs_tri_create(gs_tri_t** out, uint64_t vertex_capacity, uint32_t id_bits, int device, uint32_t flags);
+int gs_tri_destroy(gs_tri_t* h);              /* NULL is GS_OK, like gs_cc_destroy */
+int gs_tri_set_stream(gs_tri_t* h, void* hip_stream);
+int gs_tri_get_stream(gs_tri_t* h, void** hip_stream);
+int gs_tri_sync(gs_tri_t* h);
+int gs_tri_count_windows(gs_tri_t* h, const void* src, const void* dst, uint64_t n, uint64_t window_edges,
+                         uint64_t* counts, uint64_t cap, uint64_t* n_windows);
+int gs_tri_count_local(gs_tri_t* h, const void* src, const void* dst, uint64_t n,
+                       uint64_t* local, uint64_t* triangles, uint64_t* simple_edges);
+
 const char* gs_last_error(void);
 int gs_version(void);
 
