@@ -214,8 +214,9 @@ int gs_comm_unique_id(void* id, uint64_t id_bytes);
 int gs_comm_create(gs_comm_t** out, const void* unique_id, int rank, int world, int device);
 int gs_comm_create_local(gs_comm_t** comms, int world, int device);
 int gs_comm_destroy(gs_comm_t* comm);
-/* rank, world size, payload bytes sent / received, windows merged, and speculative all-gather
- * rounds whose slot a delta outgrew (each then ran one exact round) */
+/* rank, world size, payload bytes sent / received, windows merged, and speculative rounds (of the
+ * all-gather, the gather and the prefilter alike) whose slot a delta or a sender's survivors
+ * outgrew: each then ran one tail round, counted on every rank that took part in it */
 int gs_comm_info(gs_comm_t* comm, int* rank, int* world, uint64_t* bytes_sent, uint64_t* bytes_recv, uint64_t* exchanges,
                  uint64_t* overflows);
 int gs_cc_merge_window(gs_cc_t* h, gs_comm_t* comm, int mode);

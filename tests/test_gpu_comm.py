@@ -116,16 +116,34 @@ def test_local_group_vs_oracle(oracle, world, mode):
         assert len({i[5] for i in info}) == 1
 
 
-def test_local_group_young_windows_big_deltas(oracle):
-    """Windows whose deltas exceed the bulk threshold (2^21 pairs): slots folded one per call."""
+@pytest.mark.parametrize("mode", ["allgather", "gather"])
+def test_local_group_young_windows_big_deltas(oracle, mode):
+    """Windows whose deltas exceed the bulk threshold (kBulkDeltaPairs = 2^21 pairs): the all-gather's
+    slots, and the exact gather's deltas on rank 0, are folded one call per sender."""
     s, d = oracle.gen_er(0, 1 << 23, 1 << 23, 3)
     cap = 1 << 23
     W = 1 << 23                                    # one window: ~4M-pair deltas per rank
     want = oracle.run(s, d, W, partitions=2, emit=EMIT_CHECKSUM, label_cap=cap, want_final=True)
-    sums, finals, _ = _run_local(2, "allgather", s, d, cap, W)
-    for r in range(2):
+    sums, finals, _ = _run_local(2, mode, s, d, cap, W)
+    for r in (range(2) if mode == "allgather" else [0]):
         assert sums[r] == [int(x) for x in want["checksums"]]
         np.testing.assert_array_equal(finals[r], want["final"])
+
+
+def test_local_group_gather_past_the_slot_caps(oracle):
+    """17 ranks are more than a fold with per-slot capacities takes (kMaxSlotCaps = 16): every window
+    of the gather is an exact round. 10 windows of 3400 RMAT edges, 200 per rank; rank 0's emission
+    after every window vs the oracle, and no rank counts an overflow (an exact round leaves no
+    window pending, so none has a tail round)."""
+    world, W = 17, 3400
+    s, d = oracle.gen_rmat(0, 10 * W, 14, 17)
+    cap = 1 << 14
+    want = oracle.run(s, d, W, partitions=world, emit=EMIT_CHECKSUM, label_cap=cap, want_final=True)
+    sums, finals, info = _run_local(world, "gather", s, d, cap, W)
+    assert sums[0] == [int(x) for x in want["checksums"]]
+    np.testing.assert_array_equal(finals[0], want["final"])
+    assert [i[5] for i in info] == [0] * world, info
+    assert all(i[4] == 10 for i in info), info
 
 
 @pytest.mark.parametrize("sparse", [False, True])

@@ -78,6 +78,17 @@ def test_prefilter_survivor_bursts_outgrow_slots(oracle, torch_cuda):
     assert sum(r["overflows"]) > 0, r                            # the bursts did outgrow their slots
 
 
+def test_prefilter_past_the_slot_caps(oracle, torch_cuda):
+    """17 ranks are more than a fold with per-slot capacities takes (kMaxSlotCaps = 16): every window
+    is an exact round, also past the young ones (20 windows > kExactYoung). Rank 0's emission after
+    every window vs the oracle; no rank counts an overflow (an exact round leaves nothing pending)."""
+    W = 3400                                                     # 200 edges per rank and window
+    s, d = oracle.gen_rmat(0, 20 * W, 14, 17)
+    r = run_prefilter(torch_cuda, oracle, "rmat14_17ranks", s, d, W, 1 << 14, world=17, share0=1.0 / 17)
+    assert r["ok"], r
+    assert r["windows"] == 20 and r["overflows"] == [0] * 17, r
+
+
 def test_prefilter_rccl_world1(oracle, torch_cuda):
     """World 1 through RCCL: rank 0 alone (no senders), the emission of every window."""
     torch = torch_cuda

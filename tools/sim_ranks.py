@@ -94,7 +94,7 @@ def _bench_layout(P):
     return [bench.layout(_L, P, r)[1] for r in range(P)]
 
 
-# the round-6 broadcast schedule (csrc/comm.hip merge_prefilter): synchronous after the first
+# the round-6 broadcast schedule (csrc/exchange_plan.hpp bcast_sync / bcast_async): synchronous after the first
 # kBcastSync closes, then asynchronous (installed by the senders kBcastLag windows later) after every
 # close while w < 16, then after every 4th
 SYNC, LAG = int(os.environ.get("SIM_SYNC", "1")), 2      # SIM_SYNC: another synchronous prefix (A/B)
