@@ -640,8 +640,17 @@ __device__ __forceinline__ void filter_group(const FoldArgs& f, const uint32_t (
 // left (the same union); any other lane's union(H, lo) becomes union(lo, Lmin) — the same
 // components joined, over distinct words. One CAS on H per wave instead of one per lane.
 // Every lane of a live union leaves here holding its two ROOTS (fresh = its parent word kInvalid),
-// so union_edge does not walk again. Ballots and shuffles read only active lanes' values except in
-// the min reduction, whose result is checked against the lanes (no owner: nothing combined).
+// so union_edge does not walk again.
+// The callers run this in diverged code (k_fold's `g < groups`, the slot folds' `i < n`: a batch's
+// tail wave, and every wave of a small delta, is partly filled), so nothing here reads a lane that
+// may be inactive: H, Lmin and the owner come from ballots over the active lanes and from reads of
+// lanes those ballots name. Every active lane therefore sees the same H, the same Lmin and the
+// same owner, Lmin is the lo of a lane that hooks H, and a partly filled wave combines like a
+// full one. (Through round 6 Lmin was an xor-butterfly min over all 64 lanes: a reduction only in a
+// full wave. In a partial one it read inactive lanes; ds_bpermute_b32, which it compiled to, gives
+// 0 for those as the ISA manual reads, so no lane matched and nothing was combined — right by that
+// 0 alone, and that library does pass the tests named next.)
+// tests/test_gpu_pairfold.py aims batches at this function.
 __device__ __forceinline__ void combine_hooks(uint32_t* __restrict__ parent, bool halve, bool live, uint32_t& u,
                                               uint32_t& v, uint32_t& pu, uint32_t& pv, bool& skip) {
     skip = false;
@@ -668,12 +677,17 @@ __device__ __forceinline__ void combine_hooks(uint32_t* __restrict__ parent, boo
     if (!lm) return;                                                    // uniform
     const uint32_t H = __shfl(hi, __ffsll((long long)lm) - 1, 64);
     const bool same = live && hi == H;
-    if (__popcll(__ballot(same)) < 2) return;                           // uniform
-    uint32_t x = same ? lo : 0xFFFFFFFFu;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x = min(x, (uint32_t)__shfl_xor(x, off, 64));
-    const uint64_t om = __ballot(same && lo == x);
-    if (!om || !same) return;                                           // (om == 0: an inactive lane's value)
+    const uint64_t sm = __ballot(same);
+    if (__popcll(sm) < 2) return;                                       // uniform
+    // Lmin = the smallest lo among the `same` lanes: the first such lane's lo, then, while a `same`
+    // lane holds a smaller one, the first of those (ascending members: no round; a random order:
+    // ~ln 64 rounds; at most 63). Only lanes named by a ballot are read, and the lane index is
+    // wave-uniform, so every active lane ends with the same x whichever lanes are active.
+    uint32_t x = __builtin_amdgcn_readlane(lo, __ffsll((long long)sm) - 1);
+    for (uint64_t less; (less = __ballot(same && lo < x)) != 0;)
+        x = __builtin_amdgcn_readlane(lo, __ffsll((long long)less) - 1);
+    const uint64_t om = __ballot(same && lo == x);                      // never empty: x is a `same` lane's lo
+    if (!same) return;
     if ((int)__lane_id() == __ffsll((long long)om) - 1) return;         // the owner: union(H, Lmin)
     if (lo == x) {                                                      // the owner's union
         skip = true;

@@ -153,7 +153,9 @@ class Candidates:
             s = np.empty(0, dtype=bool)
         if v.size and (v.min() < 0 or k.min() < 0):
             raise ValueError("restore: negative vertex id")
-        va = np.ascontiguousarray(v.astype(dt))
+        if self.id_bits == 32 and v.size and max(v.max(), k.max()) >= 1 << 32:    # (the cast below would wrap it)
+            raise ValueError("restore: vertex id does not fit 32 bits")
+        va =np.ascontiguousarray(v.astype(dt))
         ka = np.ascontiguousarray(k.astype(dt))
         sa = np.ascontiguousarray(s.astype(np.uint8))
         call("gs_bip_restore", self.handle, 1 if success else 0, va.ctypes.data_as(ctypes.c_void_p),

@@ -148,6 +148,21 @@ def test_restore_with_key_signed_false():
     assert c.toString() == "(false,{})"
 
 
+@pytest.mark.parametrize("where", ["vertex", "key"])
+def test_restore_rejects_ids_past_32_bits(where):
+    """A 32-bit summary's restore casts its int64 ids to uint32: 2^32 + 5 would wrap to the valid id
+    5 and restore another vertex. It is refused before the cast, the summary untouched."""
+    c = Candidates(16, id_bits=32)
+    c.fold(np.array([1, 5]), np.array([2, 5]))
+    before = c.toString()
+    assert before == "(true,{1={1=(1,true), 2=(2,false)}, 5={5=(5,true)}})"
+    big = 2 ** 32 + 5
+    v, k = ([3, big], [3, 3]) if where == "vertex" else ([3, 7], [big, big])
+    with pytest.raises(ValueError):
+        c.restore(True, np.array(v, dtype=np.int64), np.array(k, dtype=np.int64), np.array([True, False]))
+    assert c.toString() == before
+
+
 # ---- GS_BIP_REFERENCE_LITERAL: the reference's Candidates rule as written (csrc/bip_literal.hpp) ----
 from bipartite import literal_run  # noqa: E402
 

@@ -78,6 +78,33 @@ def test_prefilter_survivor_bursts_outgrow_slots(oracle, torch_cuda):
     assert sum(r["overflows"]) > 0, r                            # the bursts did outgrow their slots
 
 
+def test_prefilter_survivor_star_outside_the_giant(oracle, torch_cuda):
+    """The Merger's survivor fold with many survivors on one root (combine_hooks, cc_kernels.hpp):
+    after windows that grow a giant over the upper half of the ids, a window whose sender slices are
+    stars (v_i, c_r) outside the giant — every edge survives — while rank 0's own slice hangs each
+    v_i below its own small s_i: every survivor's union hooks the fresh c_r, the larger root, and
+    the smaller roots are all different. Slices of 129 edges (two full waves and a lane) at world 3;
+    a last window joins the stars' centres to the giant."""
+    cap, k, world = 1 << 13, 129, 3
+    W = world * k
+    rng = np.random.default_rng(31)
+    g = np.arange(cap // 2, cap - 1, dtype=np.int64)                   # the giant: a path over [cap/2, cap)
+    g = g[rng.permutation(g.size)]
+    pad = (-g.size) % W
+    gs, gd = np.concatenate([g + 1, g[:pad]]), np.concatenate([g, g[:pad]])     # (padded with self-loops)
+    v = 2000 + rng.permutation(1500)[:k].astype(np.int64)
+    centres = [1000 + r for r in range(1, world)]
+    ss = np.concatenate([v] * world)
+    sd = np.concatenate([rng.permutation(1000)[:k].astype(np.int64)] + [np.full(k, c, dtype=np.int64) for c in centres])
+    js = np.resize(np.array(centres + [5], dtype=np.int64), W)
+    jd = np.resize(np.array([cap - 1, cap // 2, cap - 7], dtype=np.int64), W)
+    s, d = np.concatenate([gs, ss, js]), np.concatenate([gd, sd, jd])
+    assert s.size % W == 0
+    r = run_prefilter(torch_cuda, oracle, "survivor_star", s, d, W, cap, world=world, share0=(k + 0.5) / W)
+    assert r["ok"], r
+    assert r["windows"] == s.size // W
+
+
 def test_prefilter_past_the_slot_caps(oracle, torch_cuda):
     """17 ranks are more than a fold with per-slot capacities takes (kMaxSlotCaps = 16): every window
     is an exact round, also past the young ones (20 windows > kExactYoung). Rank 0's emission after

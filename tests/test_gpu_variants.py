@@ -17,6 +17,8 @@ configuration (the library reads its debug variables once per process; csrc/cc_a
 * test_variant_parity: every golden stream, RMAT-21, ER-21 and the giant-switch stream, per window
   vs the C oracle, under production defaults and under each forced variant (tests/variant_check.py).
 * test_fold_variants_verified: bench.py --verify (RMAT-22, 2^20-edge windows) under each variant.
+* test_pair_fold_switches: tests/test_gpu_pairfold.py with the pair folds' wave-combined hooks and
+  halving walks on and off, and the exchange / prefilter tests with them off.
 """
 import json
 import os
@@ -103,6 +105,10 @@ VARIANTS = {
     # no list-mode closes: every close after a logging fold is a bitmap or full one (the A/B knob
     # the round-4 list-close measurements ran against)
     "list_close_off": {"GSGPU_LIST_CLOSE": "0"},
+    # pair / survivor folds without wave-combined hooks, and with read-only root walks (the A/B knobs
+    # of the round-6 combine_hooks measurements)
+    "pair_combine_off": {"GSGPU_PAIR_COMBINE": "0"},
+    "pair_halve_off": {"GSGPU_PAIR_HALVE": "0"},
 }
 
 
@@ -137,3 +143,25 @@ def test_list_close_switch(name):
                                   env=env, timeout=900)
     r = _last_json(out)
     assert r["windows"] == 4096 and r["fixture_windows_equal"] and r["ok"], r
+
+
+PAIR_SWITCHES = {
+    "production": {},
+    "pair_combine_off": VARIANTS["pair_combine_off"],
+    "pair_halve_off": VARIANTS["pair_halve_off"],
+    "pair_combine_and_halve_off": {**VARIANTS["pair_combine_off"], **VARIANTS["pair_halve_off"]},
+}
+
+
+@pytest.mark.parametrize("name", list(PAIR_SWITCHES))
+def test_pair_fold_switches(name):
+    """tests/test_gpu_pairfold.py (batches aimed at combine_hooks: many pairs on one root in partly
+    filled waves) with the wave-combined hooks and the halving walks of the pair folds on
+    (production) and off (GSGPU_PAIR_COMBINE=0, GSGPU_PAIR_HALVE=0, both), each in a process of its
+    own; with a switch off also the exchange tests that fold received pairs and slots
+    (tests/test_gpu_comm.py) and the Merger's survivor folds (tests/test_gpu_prefilter.py)."""
+    cmd = [sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", os.path.join(HERE, "test_gpu_pairfold.py")]
+    if PAIR_SWITCHES[name]:                          # (-k also matches a module's file name: two whole modules)
+        cmd += [os.path.join(HERE, "test_gpu_comm.py"), os.path.join(HERE, "test_gpu_prefilter.py"), "-k",
+                "test_gpu_pairfold or test_gpu_prefilter or local_group_vs_oracle or sparse_ids_through"]
+    subprocess.check_call(cmd, env=_env(PAIR_SWITCHES[name]), timeout=900, cwd=ROOT)
