@@ -130,6 +130,10 @@ struct gs_cc {
     uint64_t warm_sample = 0;            // edges a warm count launch samples
     uint32_t warm_bcap = 0;              // keys per hash bucket
     int cus = 0;                         // compute units: k_fold_ring grid
+    // k_fold_ring's round scheduler (cc_kernels.hpp RingSteal): two sets of `cus` counters, one per
+    // 128-B line; ring launch k of the handle counts in set k & 1 and zeroes the other
+    DevBuf<uint32_t> steal;
+    uint64_t steal_launches = 0;
     void* ingest = nullptr;              // streaming text ingestion state (parse.hip), freed by ingest_free
     DevBuf<uint2> fscratch;              // partition pre-filter: per-workgroup survivor regions
     DevBuf<> fstage;                     // ... and the device copy of host edge batches
@@ -293,6 +297,11 @@ constexpr uint64_t kWarmAt = 2, kWarmEvery = 64, kWarmSample = 1ull << 23;   // 
 constexpr uint32_t kWarmBucketsMaxBits = 18;
                                                     // slower per steady window, r02_u)
 constexpr uint32_t kHotThresh = 3;                  // sightings before hot-set admission (233 -> 229 us)
+// k_fold_ring's stealable tail (cc_kernels.hpp RingSteal): the last kRingTailRows of a workgroup's
+// rows (16 per wave at the headline's 2^24-edge launches) are handed out wave round by wave round.
+// Headline ms per step on one box, parent 16.29 / 16.29 / 16.18: tail 1 no gain, 2 -0.05, 3 -0.07 / -0.08,
+// 4 -0.21, 6 -0.16, 8 -0.16, 16 (every row) -0.11 (profiles/ring_steal_ab.txt)
+constexpr uint32_t kRingTailRows = 4;
 // Young split: inside the young forest, close internally (compress + giant pick: no emission,
 // labels stay canonical) after S edges, so the rest of the young window folds with the giant
 // filter on. Round 2 measured it at capacity/16 edges: RMAT-26 window 1 1487 -> 1297 us. Round 5,
@@ -324,6 +333,8 @@ constexpr int kSmallEpt = 1;
 //   GSGPU_RING_MIN_BITS=B    ring fold + warm set from ids >= 2^B instead of 2^25 (tests at small sizes)
 //   GSGPU_YOUNG_SPLIT=S      young split after S edges (default: none; tests and A/B)
 //   GSGPU_PAIR_COMBINE=0     pair / survivor folds without wave-combined hooks (A/B)
+//   GSGPU_RING_STEAL=0       k_fold_ring with the static grid-stride loop, no stealable tail (parity, A/B;
+//                            S > 0: the last S rows of every workgroup are stealable instead of kRingTailRows)
 enum FoldMode { kFoldPlain = 0, kFoldRing = 1, kFoldAuto = 2 };
 struct DebugEnv {
     bool fold_stats = false;
@@ -338,6 +349,7 @@ struct DebugEnv {
     bool small_claim = true;                        // GSGPU_SMALL_CLAIM=0: small k_fold launches without claims (A/B)
     bool pair_combine = true;                       // GSGPU_PAIR_COMBINE=0: pair folds without combined hooks (A/B)
     uint32_t pair_halve = 1;                        // GSGPU_PAIR_HALVE=0: pair folds walk read-only (A/B)
+    uint32_t ring_steal = kRingTailRows;            // GSGPU_RING_STEAL=0: static ring loop (parity, A/B)
     DebugEnv() {
         const char* e = getenv("GSGPU_FOLD_STATS");
         fold_stats = e && atoi(e) != 0;
@@ -364,7 +376,8 @@ struct DebugEnv {
         if (e && *e) pair_combine = atoi(e) != 0;
         e = getenv("GSGPU_PAIR_HALVE");
         if (e && *e) pair_halve = atoi(e) != 0 ? 1u : 0u;
-
+        e = getenv("GSGPU_RING_STEAL");
+        if (e && *e) ring_steal = (uint32_t)std::max(0, atoi(e));
     }
 };
 static const DebugEnv& dbg() {
@@ -518,17 +531,24 @@ void launch_fold_ring(gs_cc_t* h, const IdT* a, const IdT* b, uint64_t n) {
     KTimer t(h, h->fold_timer == GS_K_FOLD ? GS_K_RING : h->fold_timer, n);
     const bool st = h->dstats != nullptr;
     const dim3 grid(grid_for(n / 4, kHotThreads, (unsigned)std::max(h->cus, 1)));
+    RingSteal rs;
+    if (h->steal && dbg().ring_steal) {
+        rs.lines = h->steal;
+        rs.nlines = (uint32_t)std::max(h->cus, 1);
+        rs.set = (uint32_t)(h->steal_launches++ & 1);
+        rs.tail = dbg().ring_steal;
+    }
     hipEvent_t stop = build ? nullptr : t.stop();
     hipEvent_t start = t.start();
     if (hot.clocks) {                                // GSGPU_RING_CLOCKS: the instrumented instance
-        if (h->mark) klaunch(k_fold_ring<IdT, true, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
-        else klaunch(k_fold_ring<IdT, false, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
+        if (h->mark) klaunch(k_fold_ring<IdT, true, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
+        else klaunch(k_fold_ring<IdT, false, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
     } else if (h->mark) {
-        if (st) klaunch(k_fold_ring<IdT, true, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
-        else klaunch(k_fold_ring<IdT, true, false>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
+        if (st) klaunch(k_fold_ring<IdT, true, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
+        else klaunch(k_fold_ring<IdT, true, false>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
     } else {
-        if (st) klaunch(k_fold_ring<IdT, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
-        else klaunch(k_fold_ring<IdT, false, false>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot);
+        if (st) klaunch(k_fold_ring<IdT, false, true>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
+        else klaunch(k_fold_ring<IdT, false, false>, grid, dim3(kHotThreads), h->stream, start, stop, a, b, f, hot, rs);
     }
     if (hot.clocks) h->ring_clock_groups = std::min<unsigned>(grid.x, kRingPhaseGroups);
     if (build) launch_warm_build(h, t.stop(), h->stream);
@@ -1177,6 +1197,9 @@ int gs_cc_create(gs_cc_t** out, const gs_cc_config* cfg) {
                 h->hot_cand.reset();
             }
             h->hot_bits = bits;
+            // the ring fold's round counters are optional too (without them: the static loop)
+            if (h->hot && h->steal.grow(2 * (size_t)std::max(h->cus, 1) * kStealLineWords, "ring round counters") != GS_OK)
+                h->steal.reset();
             // warm set: only where gbits outgrows an XCD's 4 MiB L2 (with the ring fold), its table
             // L2-resident and at most 1/8 of gbits (8-bit slots need at least 2^(B-8) buckets)
             h->warm_bits = std::min<uint32_t>(kWarmBucketsMaxBits, bits - 6);
@@ -1258,6 +1281,7 @@ int gs_cc_reset(gs_cc_t* h) {
     GS_HIP(hipMemsetAsync(h->psamp, 0xFF, 2 * kPickSamples * sizeof(uint32_t), h->stream));   // no samples yet
     if (h->hot) GS_HIP(hipMemsetAsync(h->hot, 0, kHotBuckets * sizeof(uint2), h->stream));
     if (h->hot_cand) GS_HIP(hipMemsetAsync(h->hot_cand, 0xFF, sizeof(uint32_t) << kHotCandBits, h->stream));
+    if (h->steal) GS_HIP(hipMemsetAsync(h->steal, 0, h->steal.capacity() * sizeof(uint32_t), h->stream));
     if (h->sparse) {
         hipLaunchKernelGGL(k_fill64, dim3(grid_for(1ull << h->hbits, 256, 4096)), dim3(256), 0, h->stream, h->keys,
                            (uint64_t)1 << h->hbits, kEmptyKey);

@@ -1136,17 +1136,82 @@ struct HotLaunch {
 constexpr uint32_t kRingPhaseGroups = 4096;
 __device__ unsigned long long g_ring_phase[kRingPhaseGroups][4];
 
+// ---- round scheduler of k_fold_ring ----
+// A wave round is 64 groups of 4 edges from g0 = j * stride + x * 1024 + wave * 64 (stride =
+// grid x 1024): row j, wave `wave` of the workgroup x that OWNS it — the grid-stride layout, so a
+// round's memory, its warm-count slot and its place in the admission sample do not depend on who
+// runs it. A workgroup runs all but the last `tail` of its rows itself, wave by wave, without any
+// global atomic. The wave rounds of its last `tail` rows are tickets 0..T-1 (row-major, so the
+// rounds of a ragged last row that start below `groups` are a prefix) handed out by atomicAdd on the
+// workgroup's own counter, to its own waves and, once their own tail is drained, to the waves of up
+// to kStealVictims other workgroups: a launch ends when the chip is out of rounds, not when the
+// slowest CU has done its 1/grid of them. Every ticket is handed out exactly once; nobody waits,
+// spins or polls: a wave that finds a counter at or past T goes on to the next victim and never
+// comes back, and leaves the loop after the last one.
+// Counters: two sets of `nlines` counters (>= any launch's grid), each on a 128-B line of its own.
+// Launch k counts in set k & 1 and zeroes every line of the other set, which launch k + 1 (same
+// stream) counts in: no memset, no launch between windows.
+// Line budget: a counter gets T <= 16 x tail returning atomics that hand out a round, at most one
+// more from each wave of its owner (16) and per victim list it is on (kStealVictims workgroups x
+// 16 waves) one relaxed load and at most one atomic per wave, less what the LDS `drained` flags
+// save: <= 16 x tail + 16 + 2 x 16 x kStealVictims = 208 accesses per line and launch at tail = 4
+// (the headline's 16 rows per workgroup), spread over the launch's last quarter (the per-XCD heads
+// of round 6 took ~8 K per line).
+struct RingSteal {
+    uint32_t* lines = nullptr;   // 2 x nlines counters, kStealLineWords apart; nullptr: static grid-stride loop, tail unused
+    uint32_t nlines = 0;
+    uint32_t set = 0;            // this launch's set
+    uint32_t tail = 0;           // rows per workgroup handed out by counter (>= 1 with lines)
+};
+constexpr uint32_t kStealLineWords = 32;             // 128 B
+constexpr uint32_t kStealVictims = 4;
+// victim i = 1..kStealVictims of workgroup b: b ^ 1, b ^ 3, b ^ 5, b ^ 7 — the four workgroups of
+// b's aligned group of 8 (one per XCD: workgroups go round-robin over the 8 XCDs) on the other XCD
+// parity, the neighbour first (odd XCDs end later than even ones)
+__device__ __forceinline__ uint32_t steal_victim(uint32_t b, uint32_t i) { return b ^ (2 * i - 1); }
+
+// the rounds of one launch: groups = n / 4 groups of 4 edges over `grid` workgroups of 16 waves
+struct RingRounds {
+    uint64_t groups, stride;
+    uint32_t tail;
+    // x's rows: j with j * stride + x * 1024 < groups; the first `first` run static, the rest are
+    // `tickets` wave rounds (x < grid; 0 rows past the end)
+    __device__ __forceinline__ void tail_of(uint32_t x, uint32_t& first, uint32_t& tickets) const {
+        const uint64_t base = (uint64_t)x * kHotThreads;
+        first = tickets = 0;
+        if (base >= groups) return;
+        const uint64_t rem = groups - base;
+        const uint32_t rows = (uint32_t)((rem + stride - 1) / stride);
+        const uint64_t last = rem - (uint64_t)(rows - 1) * stride;            // groups left for x's last row
+        const uint32_t lastw = (uint32_t)min((uint64_t)(kHotThreads / 64), (last + 63) / 64);
+        first = rows > tail ? rows - tail : 0;
+        tickets = (rows - 1 - first) * (kHotThreads / 64) + lastw;
+    }
+    __device__ __forceinline__ uint64_t g0(uint32_t x, uint32_t row, uint32_t wave) const {
+        return (uint64_t)row * stride + (uint64_t)x * kHotThreads + wave * 64;
+    }
+};
+
 template <typename IdT, bool MARK, bool STATS, bool CLK = false>
 __global__ __launch_bounds__(kHotThreads) void k_fold_ring(const IdT* __restrict__ a, const IdT* __restrict__ b,
-                                                           FoldArgs f, HotArgs hot) {
+                                                           FoldArgs f, HotArgs hot, RingSteal rs) {
     __shared__ __attribute__((aligned(16))) uint2 tab[kHotBuckets];
     __shared__ uint2 rings[kHotThreads / 64][kRingCap];
+    __shared__ uint32_t s_drained[kStealVictims + 1];   // victim i's tail is handed out (i = 1..)
     const uint64_t n = f.n;
     const bool clocks = CLK && threadIdx.x == 0 && blockIdx.x < kRingPhaseGroups;
     if (clocks) g_ring_phase[blockIdx.x][0] = wall_clock64();
     const bool filt = *f.giant != kInvalid;          // uniform
     if (!filt) f.sbits = nullptr;                    // the next close is a full pass (k_fold)
     else f.hbits = nullptr;
+    const bool steal = rs.lines != nullptr;          // uniform (the host passes lines only with tail >= 1)
+    if (steal) {
+        // the other counter set, for the next launch: every line, whatever that launch's grid
+        uint32_t* const other = rs.lines + (size_t)(rs.set ^ 1u) * rs.nlines * kStealLineWords;
+        for (uint32_t l = blockIdx.x + threadIdx.x * gridDim.x; l < rs.nlines; l += kHotThreads * gridDim.x)
+            __hip_atomic_store(&other[(size_t)l * kStealLineWords], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x <= kStealVictims) s_drained[threadIdx.x] = 0u;
+    }
     if (filt) lds_fill<2 * kHotBuckets>(reinterpret_cast<uint32_t*>(tab), reinterpret_cast<const uint32_t*>(hot.table), 2 * kHotBuckets);
     // the root gbits were built for (= the giant's label at the last close); survivors' giant
     // flags use it in place of a parent[] read (union_group_g). Off (kInvalid) without a filter
@@ -1197,8 +1262,57 @@ __global__ __launch_bounds__(kHotThreads) void k_fold_ring(const IdT* __restrict
         cnt += wtot;
         if (cnt >= 64) ring_flush<MARK, STATS>(f, ring, cnt, cnt - 64, st, gR);
     };
-    for (uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); g0 < groups; g0 += stride)
+    // the scheduler (RingSteal above): rows [0, first) static, then tickets of x = this workgroup,
+    // then of the victims. Everything here is wave-uniform.
+    const uint32_t wave = threadIdx.x >> 6;
+    const RingRounds rr{groups, stride, rs.tail};
+    uint32_t* const ctrs = rs.lines + (size_t)rs.set * rs.nlines * kStealLineWords;
+    uint32_t x = blockIdx.x, vi = 0, first = 0, tickets = 0;
+    if (steal) {
+        rr.tail_of(x, first, tickets);
+    } else {                                         // all of this wave's rounds, no tail
+        const uint64_t base = rr.g0(x, 0, wave);
+        first = base < groups ? (uint32_t)((groups - base + stride - 1) / stride) : 0;
+    }
+    const uint32_t own_first = first;
+    auto take = [&]() -> uint32_t {                  // the next ticket of x (one returning atomic per wave)
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&ctrs[(size_t)x * kStealLineWords], 1u);
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    };
+    uint32_t t = 0, tn = 0;
+    bool started = false;
+    for (uint32_t j = 0;;) {
+        uint64_t g0;
+        if (j < own_first) {
+            g0 = rr.g0(blockIdx.x, j, wave);
+            ++j;
+        } else {
+            if (!steal) break;
+            t = started ? tn : take();
+            started = true;
+            if (t >= tickets) {                      // x is handed out: the next victim with rounds left
+                if (vi) __hip_atomic_store(&s_drained[vi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                bool found = false;
+                while (!found && ++vi <= kStealVictims) {
+                    x = steal_victim(blockIdx.x, vi);
+                    if (x >= gridDim.x || __hip_atomic_load(&s_drained[vi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) continue;
+                    rr.tail_of(x, first, tickets);
+                    // peek before the atomic: a drained victim costs a load, not a returning atomic
+                    // (a stale low value only costs the atomic: the counter never goes down in a launch)
+                    if (__hip_atomic_load(&ctrs[(size_t)x * kStealLineWords], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < tickets) {
+                        t = take();
+                        found = t < tickets;
+                    }
+                    if (!found) __hip_atomic_store(&s_drained[vi], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (!found) break;
+            }
+            tn = take();                             // the round after this one: its latency hides behind this round
+            g0 = rr.g0(x, first + t / (kHotThreads / 64), t % (kHotThreads / 64));
+        }
         wave_round(g0);
+    }
     __shared__ uint32_t s_mcnt;
     __shared__ unsigned long long s_mbase;
     if (CLK) {
