@@ -7,6 +7,8 @@
 //   SummaryBulkAggregation         SummaryBulkAggregation.java:46-131 (+ Merger, SummaryAggregation.java:94-136)
 //   ConnectedComponents(long)      library/ConnectedComponents.java:44-55
 //   SimpleEdgeStream::aggregate    SimpleEdgeStream.java:100-102
+//   DegreeSummary                  SimpleEdgeStream.java:413-478 (getDegrees / getInDegrees / getOutDegrees),
+//                                  example/DegreeDistribution.java:70-132 (additions and deletions)
 // Errors: the Java UDFs throw Exception; here a failing ABI call throws gelly::streaming::GsError
 // carrying the GS_ERR_* code and gs_last_error() text.
 #pragma once
@@ -385,6 +387,90 @@ private:
     uint64_t cap_;
     int device_;
     uint64_t window_edges_;
+};
+
+// Vertex degrees and their distribution on the device (gs_deg_*): degree[v] of every vertex with
+// degree > 0 and count[d] = vertices of degree d, folded in count windows of edge events
+// (additions and deletions; x -> max(x + change, 0) per vertex event). K = int32_t or int64_t ids
+// in [0, capacity). flags: GS_DEG_OUT | GS_DEG_IN | GS_DEG_SORT_ALL.
+template <typename K>
+class DegreeSummary {
+    static_assert(std::is_same<K, int32_t>::value || std::is_same<K, int64_t>::value, "K must be int32_t or int64_t");
+
+public:
+    using Stats = gs_deg_window_stats;
+    explicit DegreeSummary(uint64_t capacity, int device = 0, uint32_t flags = 0, uint32_t dense_degrees = 0) {
+        check(gs_deg_create(&h_, capacity, sizeof(K) * 8, device, flags, dense_degrees), "gs_deg_create");
+    }
+    ~DegreeSummary() { gs_deg_destroy(h_); }
+    DegreeSummary(const DegreeSummary&) = delete;
+    DegreeSummary& operator=(const DegreeSummary&) = delete;
+    DegreeSummary(DegreeSummary&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+
+    gs_deg_t* handle() const { return h_; }
+    void reset() { check(gs_deg_reset(h_), "gs_deg_reset"); }
+    void sync() { check(gs_deg_sync(h_), "gs_deg_sync"); }
+    void setStream(void* hip_stream) { check(gs_deg_set_stream(h_, hip_stream), "gs_deg_set_stream"); }
+
+    // one window; add: 1 = EDGE_ADDITION, 0 = EDGE_DELETION per event, or null for additions only
+    void foldWindow(const K* src, const K* dst, const uint8_t* add, uint64_t n) {
+        check(gs_deg_fold_window(h_, src, dst, add, n), "gs_deg_fold_window");
+    }
+    // every window of window_edges events; one Stats per window
+    std::vector<Stats> foldWindows(const K* src, const K* dst, const uint8_t* add, uint64_t n, uint64_t window_edges) {
+        std::vector<Stats> st(window_edges ? (n + window_edges - 1) / window_edges : 0);
+        uint64_t nw = 0;
+        check(gs_deg_fold_windows(h_, src, dst, add, n, window_edges, st.data(), st.size(), &nw), "gs_deg_fold_windows");
+        st.resize(nw);
+        return st;
+    }
+    Stats stats() {
+        Stats s{};
+        check(gs_deg_stats(h_, &s), "gs_deg_stats");
+        return s;
+    }
+    // (vertex, degree) ordered by vertex: the whole map, or the last window's delta (0 = removed)
+    void degrees(std::vector<K>& v, std::vector<uint32_t>& d) { pairs(gs_deg_emit_degrees, "gs_deg_emit_degrees", v, d); }
+    void degreesDelta(std::vector<K>& v, std::vector<uint32_t>& d) {
+        pairs(gs_deg_emit_degrees_delta, "gs_deg_emit_degrees_delta", v, d);
+    }
+    // (degree, count) ordered by degree: the keys with a count, or the last window's delta (may be 0)
+    void distribution(std::vector<uint32_t>& d, std::vector<uint64_t>& c) {
+        pairs(gs_deg_emit_distribution, "gs_deg_emit_distribution", d, c);
+    }
+    void distributionDelta(std::vector<uint32_t>& d, std::vector<uint64_t>& c) {
+        pairs(gs_deg_emit_distribution_delta, "gs_deg_emit_distribution_delta", d, c);
+    }
+    uint32_t find(K v) {
+        uint32_t d = 0;
+        check(gs_deg_find(h_, &v, &d, 1), "gs_deg_find");
+        return d;
+    }
+    void snapshot(std::vector<K>& v, std::vector<uint32_t>& d) { degrees(v, d); }
+    void restore(const std::vector<K>& v, const std::vector<uint32_t>& d) {
+        if (v.size() != d.size()) throw std::invalid_argument("DegreeSummary::restore: sizes differ");
+        check(gs_deg_restore(h_, v.data(), d.data(), v.size()), "gs_deg_restore");
+    }
+
+private:
+    template <typename F, typename A, typename B>
+    void pairs(F fn, const char* name, std::vector<A>& a, std::vector<B>& b) {
+        uint64_t n = 0, cap = 64;
+        for (;;) {
+            a.resize(cap);
+            b.resize(cap);
+            const int rc = fn(h_, a.data(), b.data(), cap, &n);
+            if (rc == GS_ERR_CAPACITY && n > cap) {
+                cap = n;
+                continue;
+            }
+            check(rc, name);
+            break;
+        }
+        a.resize(n);
+        b.resize(n);
+    }
+    gs_deg_t* h_ = nullptr;
 };
 
 }  // namespace streaming

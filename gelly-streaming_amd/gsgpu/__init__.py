@@ -8,9 +8,11 @@ from .aggregation import (SimpleEdgeStream, SummaryBulkAggregation, ConnectedCom
                           SummaryTreeReduce, ConnectedComponentsTree)
 from .bipartite import Candidates, BipartitenessCheck  # noqa: F401
 from .triangles import TriangleCounter, WindowTriangles  # noqa: F401
+from .degrees import DegreeSummary, DegreeDistribution  # noqa: F401
 from .comm import Comm  # noqa: F401
 
 __all__ = ["DisjointSet", "UpdateCC", "CombineCC", "combine_cc", "SimpleEdgeStream",
            "SummaryBulkAggregation", "ConnectedComponents", "SummaryTreeReduce", "ConnectedComponentsTree",
-           "Candidates", "BipartitenessCheck", "TriangleCounter", "WindowTriangles", "GsError", "GsgpuUnavailable",
+           "Candidates", "BipartitenessCheck", "TriangleCounter", "WindowTriangles", "DegreeSummary",
+           "DegreeDistribution", "GsError", "GsgpuUnavailable",
            "available", "lib"]

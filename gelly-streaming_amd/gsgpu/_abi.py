@@ -27,6 +27,7 @@ GS_CC_TRACK_MARKS = 1
 GS_CC_SPARSE_IDS = 2
 GS_BIP_REFERENCE_LITERAL = 1
 GS_TRI_ORIENT_BY_ID = 1
+GS_DEG_OUT, GS_DEG_IN, GS_DEG_SORT_ALL, GS_DEG_COUNT = 1, 2, 4, 8
 
 GS_K_FOLD, GS_K_COMPRESS, GS_K_MERGE, GS_K_EXPORT, GS_K_RING = 0, 1, 2, 3, 4
 GS_MERGE_ALLGATHER, GS_MERGE_GATHER, GS_MERGE_TREE, GS_MERGE_PREFILTER = 0, 1, 2, 3
@@ -50,6 +51,9 @@ EXPORTED_SYMBOLS = (
     "gs_bip_emit_pairs", "gs_bip_create_ex", "gs_bip_restore",
     "gs_tri_create", "gs_tri_destroy", "gs_tri_set_stream", "gs_tri_get_stream", "gs_tri_sync",
     "gs_tri_count_windows", "gs_tri_count_local",
+    "gs_deg_create", "gs_deg_destroy", "gs_deg_reset", "gs_deg_set_stream", "gs_deg_get_stream", "gs_deg_sync",
+    "gs_deg_fold_window", "gs_deg_fold_windows", "gs_deg_stats", "gs_deg_path_counts", "gs_deg_emit_degrees", "gs_deg_emit_degrees_delta",
+    "gs_deg_emit_distribution", "gs_deg_emit_distribution_delta", "gs_deg_find", "gs_deg_restore",
     "gs_comm_unique_id", "gs_comm_create", "gs_comm_create_local", "gs_comm_destroy", "gs_comm_info",
     "gs_cc_merge_window", "gs_cc_fold_windows",
     "gs_last_error", "gs_version",
@@ -86,6 +90,11 @@ class GsCcConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("id_bits", ctypes.c_uint32),
                 ("vertex_capacity", ctypes.c_uint64), ("device", ctypes.c_int32),
                 ("flags", ctypes.c_uint32), ("staging_edges", ctypes.c_uint64)]
+
+
+class GsDegWindowStats(ctypes.Structure):
+    _fields_ = [("n_vertices", ctypes.c_uint64), ("n_degrees", ctypes.c_uint64),
+                ("max_degree", ctypes.c_uint64), ("checksum", ctypes.c_uint64)]
 
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -169,6 +178,22 @@ def lib() -> ctypes.CDLL:
         "gs_tri_sync": [vp],
         "gs_tri_count_windows": [vp, vp, vp, u64, u64, vp, u64, P(u64)],
         "gs_tri_count_local": [vp, vp, vp, u64, vp, P(u64), P(u64)],
+        "gs_deg_create": [P(vp), u64, u32, i32, u32, u32],
+        "gs_deg_destroy": [vp],
+        "gs_deg_reset": [vp],
+        "gs_deg_set_stream": [vp, vp],
+        "gs_deg_get_stream": [vp, P(vp)],
+        "gs_deg_sync": [vp],
+        "gs_deg_fold_window": [vp, vp, vp, vp, u64],
+        "gs_deg_fold_windows": [vp, vp, vp, vp, u64, u64, vp, u64, P(u64)],
+        "gs_deg_stats": [vp, P(GsDegWindowStats)],
+        "gs_deg_path_counts": [vp, P(u64), P(u64), P(u64), P(u64)],
+        "gs_deg_emit_degrees": [vp, vp, vp, u64, P(u64)],
+        "gs_deg_emit_degrees_delta": [vp, vp, vp, u64, P(u64)],
+        "gs_deg_emit_distribution": [vp, vp, vp, u64, P(u64)],
+        "gs_deg_emit_distribution_delta": [vp, vp, vp, u64, P(u64)],
+        "gs_deg_find": [vp, vp, vp, u64],
+        "gs_deg_restore": [vp, vp, vp, u64],
         "gs_comm_unique_id": [vp, u64],
         "gs_comm_create": [P(vp), vp, i32, i32, i32],
         "gs_comm_create_local": [P(vp), i32, i32],

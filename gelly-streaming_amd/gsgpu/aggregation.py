@@ -37,9 +37,11 @@ from .summary import CombineCC, DisjointSet, UpdateCC
 
 
 class SimpleEdgeStream:
-    """An edge stream in arrival order: src[i] -> dst[i], optional event timestamps (ms)."""
+    """An edge stream in arrival order: src[i] -> dst[i], optional event timestamps (ms) and
+    optional event types (``events[i]`` true = EDGE_ADDITION, false = EDGE_DELETION; additions
+    where absent)."""
 
-    def __init__(self, src, dst, timestamps: Optional[Sequence[int]] = None):
+    def __init__(self, src, dst, timestamps: Optional[Sequence[int]] = None, events=None):
         self.src = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
         self.dst = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
         if self.src.shape != self.dst.shape:
@@ -47,6 +49,9 @@ class SimpleEdgeStream:
         self.timestamps = None if timestamps is None else np.asarray(timestamps, dtype=np.int64)
         if self.timestamps is not None and self.timestamps.shape != self.src.shape:
             raise ValueError("timestamps length mismatch")
+        self.events = None if events is None else np.ascontiguousarray(np.asarray(events).astype(bool).astype(np.uint8))
+        if self.events is not None and self.events.shape != self.src.shape:
+            raise ValueError("events length mismatch")
 
     def __len__(self) -> int:
         return int(self.src.size)
@@ -54,6 +59,22 @@ class SimpleEdgeStream:
     def aggregate(self, summary_aggregation: "SummaryBulkAggregation") -> Iterator[DisjointSet]:
         """GraphStream.aggregate (GraphStream.java:139-140)."""
         return summary_aggregation.run(self)
+
+    def getDegrees(self, window_edges: int = 1, **kw):
+        """SimpleEdgeStream.getDegrees (SimpleEdgeStream.java:413-416): per count window, the
+        (vertex, degree) pairs of the vertices whose degree changed (gsgpu.degrees)."""
+        from .degrees import degree_stream
+        return degree_stream(self, "all", window_edges, **kw)
+
+    def getInDegrees(self, window_edges: int = 1, **kw):
+        """SimpleEdgeStream.getInDegrees (:424-427): targets only."""
+        from .degrees import degree_stream
+        return degree_stream(self, "in", window_edges, **kw)
+
+    def getOutDegrees(self, window_edges: int = 1, **kw):
+        """SimpleEdgeStream.getOutDegrees (:435-438): sources only."""
+        from .degrees import degree_stream
+        return degree_stream(self, "out", window_edges, **kw)
 
     def windows(self, time_millis: int, window_edges: Optional[int]) -> List[slice]:
         n = len(self)

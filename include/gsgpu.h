@@ -371,6 +371,88 @@ int gs_tri_count_windows(gs_tri_t* h, const void* src, const void* dst, uint64_t
 int gs_tri_count_local(gs_tri_t* h, const void* src, const void* dst, uint64_t n,
                        uint64_t* local, uint64_t* triangles, uint64_t* simple_edges);
 
+/* ---- streaming degrees and DegreeDistribution, with edge deletions ----
+ * (SimpleEdgeStream.getDegrees / getInDegrees / getOutDegrees, SimpleEdgeStream.java:413-478;
+ *  example/DegreeDistribution.java:70-132, the reference's consumer of EventType)
+ * The summary: degree[v] of every vertex with degree > 0, and count[d] = vertices of degree d.
+ * An event (src, dst, add) is two vertex events in stream order, src then dst (GS_DEG_OUT keeps
+ * only sources, GS_DEG_IN only targets; neither or both: both). A vertex event changes the degree
+ * x of its vertex to max(x + change, 0), change = +1 | -1, absent = 0: a deletion at an absent
+ * vertex is ignored, a vertex whose degree reaches 0 leaves the map (VertexDegreeCounts.flatMap).
+ * A self-loop adds 2 (1 with GS_DEG_IN or GS_DEG_OUT). The library works in count windows: after a
+ * window the summary equals the reference's maps after the same prefix of the stream, for any
+ * stream, one that deletes more than was added included. Dense ids in [0, vertex_capacity),
+ * vertex_capacity <= 2^32 - 1, id_bits 32 or 64. add: nullable uint8 array (1 = addition, 0 =
+ * deletion; NULL = all additions). src / dst / add host or device, as for gs_cc_fold.
+ * Per-window emissions (the reference emits per record):
+ *   degree delta        the vertices whose degree after the window differs from before it, with
+ *                       their new degree (0 = removed), ordered by vertex
+ *   distribution delta  the degree keys whose count after the window differs from before it, with
+ *                       their new count (may be 0), ordered by degree
+ * Both are the reference's LAST record of that key within the window, for keys with a net change.
+ * The reference's records for keys that end the window where they began are not reproduced. With
+ * one-event windows the deltas are the reference's records (DegreeDistributionITCase, TestGetDegrees).
+ *   flags: GS_DEG_OUT, GS_DEG_IN (above). Two paths compute a window, with equal results:
+ *          GS_DEG_SORT_ALL: every vertex event takes the exact path (sort by vertex and position,
+ *          ordered segmented composition); GS_DEG_COUNT: the counting path (one atomic add per
+ *          vertex event on a per-vertex accumulator, plain sum at the close), which sends only the
+ *          events of vertices a window could clamp through the exact path. With neither flag the
+ *          library takes the one measured faster, which is sort-everything.
+ *   dense_degrees: count[d] is a dense array for d < dense_degrees (0 = 65536), a hash table of
+ *          at most 2^20 slots above it.
+ *   gs_deg_fold_window   one window: fold and close.
+ *   gs_deg_fold_windows  every window of window_edges events (the last may be shorter); one
+ *          gs_deg_window_stats per window into the host array stats (cap entries); *n_windows =
+ *          ceil(n / window_edges); cap < that: GS_ERR_CAPACITY, nothing folded; n == 0: GS_OK, 0
+ *          windows. One host wait, at the end; with GS_DEG_COUNT a window with deletions (add !=
+ *          NULL) waits once more, for a small read: the events of the vertices it could clamp.
+ *   gs_deg_stats         the same numbers for the current summary. checksum = sum mod 2^64 over
+ *          vertices with degree > 0 of splitmix64(v ^ splitmix64(degree ^ 0xD1B54A32D192ED03)).
+ *   gs_deg_emit_degrees / _degrees_delta       (vertex, degree) ordered by vertex; vertices id_bits
+ *          wide, degrees uint32; host or device arrays of cap entries; *n_out = the number of
+ *          entries; cap < that: GS_ERR_CAPACITY, nothing written.
+ *   gs_deg_emit_distribution / _distribution_delta   (degree, count) ordered by degree; uint32 /
+ *          uint64. The deltas are those of the last window folded (of a gs_deg_fold_windows call:
+ *          its last window); empty after gs_deg_reset / gs_deg_restore.
+ *   gs_deg_find          degrees[i] = degree of ids[i], 0 for an absent vertex.
+ *   gs_deg_restore       the summary becomes a snapshot's: the n pairs gs_deg_emit_degrees wrote, in
+ *          any order; distribution, statistics and checksum are rebuilt on the device (the Merger's
+ *          checkpoint, as gs_bip_restore). A repeated vertex or a degree of 0: GS_ERR_INVALID; an
+ *          id outside the capacity: GS_ERR_RANGE; the summary is unchanged then.
+ * Failures: an id outside [0, vertex_capacity) in a window: GS_ERR_RANGE; that window and the later
+ * ones of the call are not folded and the summary is as after the last window before it. Limits:
+ * degrees are 32 bits wide: a call is refused with GS_ERR_CAPACITY, before anything is folded, when
+ * (largest restored degree) + 2 x (events folded since the last reset or restore, this call
+ * included) could pass 2^32 - 1; likewise when more than (table slots) / 4 distinct degrees >=
+ * dense_degrees are possible. A window holds at most 2^30 - 1 events; vertex, position and sign
+ * must fit a 64-bit sort key (GS_ERR_UNSUPPORTED: capacity above 2^31 with windows above 2^29). */
+typedef struct gs_deg gs_deg_t;
+enum { GS_DEG_OUT = 1, GS_DEG_IN = 2, GS_DEG_SORT_ALL = 4, GS_DEG_COUNT = 8 };
+typedef struct gs_deg_window_stats {
+    uint64_t n_vertices;        /* vertices with degree > 0 */
+    uint64_t n_degrees;         /* degree keys with count > 0 */
+    uint64_t max_degree;
+    uint64_t checksum;
+} gs_deg_window_stats;
+int gs_deg_create(gs_deg_t** out, uint64_t vertex_capacity, uint32_t id_bits, int device, uint32_t flags, uint32_t dense_degrees);
+int gs_deg_destroy(gs_deg_t* h);              /* NULL is GS_OK */
+int gs_deg_reset(gs_deg_t* h);
+int gs_deg_set_stream(gs_deg_t* h, void* hip_stream);
+int gs_deg_get_stream(gs_deg_t* h, void** hip_stream);
+int gs_deg_sync(gs_deg_t* h);
+int gs_deg_fold_window(gs_deg_t* h, const void* src, const void* dst, const uint8_t* add, uint64_t n);
+int gs_deg_fold_windows(gs_deg_t* h, const void* src, const void* dst, const uint8_t* add, uint64_t n, uint64_t window_edges,
+                        gs_deg_window_stats* stats, uint64_t cap, uint64_t* n_windows);
+int gs_deg_stats(gs_deg_t* h, gs_deg_window_stats* stats);
+/* since create: windows folded, those that took the exact path, vertex events, those that were sorted (any may be NULL) */
+int gs_deg_path_counts(gs_deg_t* h, uint64_t* windows, uint64_t* exact_windows, uint64_t* vertex_events, uint64_t* exact_events);
+int gs_deg_emit_degrees(gs_deg_t* h, void* vertices, uint32_t* degrees, uint64_t cap, uint64_t* n_out);
+int gs_deg_emit_degrees_delta(gs_deg_t* h, void* vertices, uint32_t* degrees, uint64_t cap, uint64_t* n_out);
+int gs_deg_emit_distribution(gs_deg_t* h, uint32_t* degrees, uint64_t* counts, uint64_t cap, uint64_t* n_out);
+int gs_deg_emit_distribution_delta(gs_deg_t* h, uint32_t* degrees, uint64_t* counts, uint64_t cap, uint64_t* n_out);
+int gs_deg_find(gs_deg_t* h, const void* ids, uint32_t* degrees, uint64_t n);
+int gs_deg_restore(gs_deg_t* h, const void* vertices, const uint32_t* degrees, uint64_t n);
+
 const char* gs_last_error(void);
 int gs_version(void);
 
