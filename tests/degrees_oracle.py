@@ -7,6 +7,8 @@
 (b) ``WindowOracle``: the windowed restatement the library follows: per window and vertex the ordered
     composition (A, B) of its steps x -> max(x + a, b), new = max(old + A, B); next to it the plain
     sum old + plus - minus and the at-risk test (the window's deletions at v exceed old).
+    ``record`` turns a degree vector into a window's record (degrees, distribution, both deltas,
+    stats); tests/degree_streams.py builds its records with it too.
 """
 import numpy as np
 
@@ -162,29 +164,37 @@ class WindowOracle:
         return self.record(before)
 
     def record(self, before=None):
-        deg = self.deg
-        vs = np.nonzero(deg)[0]
-        dist = np.bincount(deg[vs]) if vs.size else np.zeros(1, dtype=np.int64)
-        ds = np.nonzero(dist)[0]
-        rec = {"degrees": (vs.tolist(), deg[vs].tolist()),
-               "distribution": (ds.tolist(), dist[ds].tolist()),
-               "stats": {"n_vertices": int(vs.size), "n_degrees": int(ds.size),
-                         "max_degree": int(deg.max()) if deg.size else 0,
-                         "checksum": checksum_arrays(vs, deg[vs])}}
-        if before is not None:
-            ch = np.nonzero(deg != before)[0]
-            rec["degrees_delta"] = (ch.tolist(), deg[ch].tolist())
-            bvs = np.nonzero(before)[0]
-            bdist = np.bincount(before[bvs]) if bvs.size else np.zeros(1, dtype=np.int64)
-            m = max(dist.size, bdist.size)
-            x = np.zeros(m, dtype=np.int64)
-            y = np.zeros(m, dtype=np.int64)
-            x[:dist.size] = dist
-            y[:bdist.size] = bdist
-            x[0] = y[0] = 0
-            dk = np.nonzero(x != y)[0]
-            rec["distribution_delta"] = (dk.tolist(), x[dk].tolist())
-        return rec
+        return record(self.deg, before)
+
+
+def record(deg, before=None, arrays=False):
+    """The record of a degree vector: degrees, distribution, stats and, given the vector before the
+    window, both deltas. Pairs of lists, or of numpy arrays when ``arrays`` (large capacities)."""
+    deg = np.asarray(deg, dtype=np.int64)
+    out = (lambda a, b: (a, b)) if arrays else (lambda a, b: (a.tolist(), b.tolist()))
+    vs = np.nonzero(deg)[0]
+    dist = np.bincount(deg[vs]) if vs.size else np.zeros(1, dtype=np.int64)
+    ds = np.nonzero(dist)[0]
+    rec = {"degrees": out(vs, deg[vs]),
+           "distribution": out(ds, dist[ds]),
+           "stats": {"n_vertices": int(vs.size), "n_degrees": int(ds.size),
+                     "max_degree": int(deg.max()) if deg.size else 0,
+                     "checksum": checksum_arrays(vs, deg[vs])}}
+    if before is not None:
+        before = np.asarray(before, dtype=np.int64)
+        ch = np.nonzero(deg != before)[0]
+        rec["degrees_delta"] = out(ch, deg[ch])
+        bvs = np.nonzero(before)[0]
+        bdist = np.bincount(before[bvs]) if bvs.size else np.zeros(1, dtype=np.int64)
+        m = max(dist.size, bdist.size)
+        x = np.zeros(m, dtype=np.int64)
+        y = np.zeros(m, dtype=np.int64)
+        x[:dist.size] = dist
+        y[:bdist.size] = bdist
+        x[0] = y[0] = 0
+        dk = np.nonzero(x != y)[0]
+        rec["distribution_delta"] = out(dk, x[dk])
+    return rec
 
 
 def random_events(nv, n, p_add, seed):
