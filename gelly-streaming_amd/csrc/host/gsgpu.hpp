@@ -473,5 +473,92 @@ private:
     gs_deg_t* h_ = nullptr;
 };
 
+// Neighbourhood slices on the device (gs_slice_*): SimpleEdgeStream.slice(size, direction) ->
+// SnapshotStream. A window of edges (src, dst, value) is grouped by vertex (direction GS_SLICE_OUT:
+// sources, GS_SLICE_IN: targets, GS_SLICE_ALL: both ends), rows in arrival order; reduceOnEdges
+// reduces every row's values with a built-in op (GS_SLICE_SUM ... GS_SLICE_LAST), rows() emits the
+// neighbourhoods as CSR for applyOnNeighbors-style host code. K = int32_t or int64_t ids in
+// [0, capacity); values are int64_t (the reference's Long). Records are ordered by vertex.
+template <typename K>
+class SnapshotStream {
+    static_assert(std::is_same<K, int32_t>::value || std::is_same<K, int64_t>::value, "K must be int32_t or int64_t");
+
+public:
+    using Stats = gs_slice_window_stats;
+    explicit SnapshotStream(uint64_t capacity, uint32_t direction = GS_SLICE_OUT, int device = 0) {
+        check(gs_slice_create(&h_, capacity, sizeof(K) * 8, device, direction), "gs_slice_create");
+    }
+    ~SnapshotStream() { gs_slice_destroy(h_); }
+    SnapshotStream(const SnapshotStream&) = delete;
+    SnapshotStream& operator=(const SnapshotStream&) = delete;
+    SnapshotStream(SnapshotStream&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+
+    gs_slice_t* handle() const { return h_; }
+    void sync() { check(gs_slice_sync(h_), "gs_slice_sync"); }
+    void setStream(void* hip_stream) { check(gs_slice_set_stream(h_, hip_stream), "gs_slice_set_stream"); }
+
+    // the slice of one window; val may be null (then only GS_SLICE_COUNT applies)
+    void window(const K* src, const K* dst, const int64_t* val, uint64_t n) {
+        check(gs_slice_window(h_, src, dst, val, n), "gs_slice_window");
+    }
+    // one (vertex, value) per row of the slice held
+    void reduceOnEdges(int op, std::vector<K>& v, std::vector<int64_t>& x) {
+        uint64_t n = 0, cap = 64;
+        for (;;) {
+            v.resize(cap);
+            x.resize(cap);
+            const int rc = gs_slice_reduce(h_, op, v.data(), x.data(), cap, &n);
+            if (rc == GS_ERR_CAPACITY && n > cap) {
+                cap = n;
+                continue;
+            }
+            check(rc, "gs_slice_reduce");
+            break;
+        }
+        v.resize(n);
+        x.resize(n);
+    }
+    // the slice as CSR: row r is offsets[r] .. offsets[r + 1] of neighbours and values, in arrival order
+    void rows(std::vector<K>& vertices, std::vector<uint64_t>& offsets, std::vector<K>& neighbours, std::vector<int64_t>& values,
+              bool with_values = true) {
+        uint64_t nv = 0, ne = 0, none = 0;
+        const int rc = gs_slice_rows(h_, nullptr, &none, nullptr, nullptr, 0, 0, &nv, &ne);       // the sizes
+        if (rc != GS_ERR_CAPACITY) check(rc, "gs_slice_rows");
+        vertices.resize(nv);
+        offsets.assign(nv + 1, 0);
+        neighbours.resize(ne);
+        values.resize(with_values ? ne : 0);
+        check(gs_slice_rows(h_, vertices.data(), offsets.data(), neighbours.data(), with_values ? values.data() : nullptr, nv, ne,
+                            &nv, &ne), "gs_slice_rows");
+    }
+    Stats stats(int op) {
+        Stats s{};
+        check(gs_slice_stats(h_, op, &s), "gs_slice_stats");
+        return s;
+    }
+    // every window of window_edges edges in one call: the records concatenated, window w at
+    // offsets[w] .. offsets[w + 1]; one Stats per window
+    std::vector<Stats> reduceWindows(const K* src, const K* dst, const int64_t* val, uint64_t n, uint64_t window_edges, int op,
+                                     uint32_t direction, std::vector<K>& v, std::vector<int64_t>& x, std::vector<uint64_t>& offsets) {
+        const uint64_t nw = window_edges ? (n + window_edges - 1) / window_edges : 0;
+        const uint64_t cap = direction == GS_SLICE_ALL ? 2 * n : n;      // (at most one record per entry)
+        std::vector<Stats> st(nw);
+        v.resize(cap);
+        x.resize(cap);
+        offsets.assign(nw + 1, 0);
+        uint64_t got = 0;
+        check(gs_slice_reduce_windows(h_, src, dst, val, n, window_edges, op, v.data(), x.data(), cap, offsets.data(), st.data(), nw,
+                                      &got), "gs_slice_reduce_windows");
+        st.resize(got);
+        offsets.resize(got + 1);
+        v.resize(offsets[got]);
+        x.resize(offsets[got]);
+        return st;
+    }
+
+private:
+    gs_slice_t* h_ = nullptr;
+};
+
 }  // namespace streaming
 }  // namespace gelly

@@ -9,10 +9,11 @@ from .aggregation import (SimpleEdgeStream, SummaryBulkAggregation, ConnectedCom
 from .bipartite import Candidates, BipartitenessCheck  # noqa: F401
 from .triangles import TriangleCounter, WindowTriangles  # noqa: F401
 from .degrees import DegreeSummary, DegreeDistribution  # noqa: F401
+from .slices import SnapshotStream  # noqa: F401
 from .comm import Comm  # noqa: F401
 
 __all__ = ["DisjointSet", "UpdateCC", "CombineCC", "combine_cc", "SimpleEdgeStream",
            "SummaryBulkAggregation", "ConnectedComponents", "SummaryTreeReduce", "ConnectedComponentsTree",
            "Candidates", "BipartitenessCheck", "TriangleCounter", "WindowTriangles", "DegreeSummary",
-           "DegreeDistribution", "GsError", "GsgpuUnavailable",
+           "DegreeDistribution", "SnapshotStream", "GsError", "GsgpuUnavailable",
            "available", "lib"]

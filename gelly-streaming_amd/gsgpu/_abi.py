@@ -28,6 +28,8 @@ GS_CC_SPARSE_IDS = 2
 GS_BIP_REFERENCE_LITERAL = 1
 GS_TRI_ORIENT_BY_ID = 1
 GS_DEG_OUT, GS_DEG_IN, GS_DEG_SORT_ALL, GS_DEG_COUNT = 1, 2, 4, 8
+GS_SLICE_OUT, GS_SLICE_IN, GS_SLICE_ALL = 0, 1, 2
+GS_SLICE_SUM, GS_SLICE_MIN, GS_SLICE_MAX, GS_SLICE_COUNT, GS_SLICE_FIRST, GS_SLICE_LAST = 0, 1, 2, 3, 4, 5
 
 GS_K_FOLD, GS_K_COMPRESS, GS_K_MERGE, GS_K_EXPORT, GS_K_RING = 0, 1, 2, 3, 4
 GS_MERGE_ALLGATHER, GS_MERGE_GATHER, GS_MERGE_TREE, GS_MERGE_PREFILTER = 0, 1, 2, 3
@@ -54,6 +56,8 @@ EXPORTED_SYMBOLS = (
     "gs_deg_create", "gs_deg_destroy", "gs_deg_reset", "gs_deg_set_stream", "gs_deg_get_stream", "gs_deg_sync",
     "gs_deg_fold_window", "gs_deg_fold_windows", "gs_deg_stats", "gs_deg_path_counts", "gs_deg_emit_degrees", "gs_deg_emit_degrees_delta",
     "gs_deg_emit_distribution", "gs_deg_emit_distribution_delta", "gs_deg_find", "gs_deg_restore",
+    "gs_slice_create", "gs_slice_destroy", "gs_slice_set_stream", "gs_slice_get_stream", "gs_slice_sync",
+    "gs_slice_window", "gs_slice_reduce", "gs_slice_rows", "gs_slice_stats", "gs_slice_reduce_windows",
     "gs_comm_unique_id", "gs_comm_create", "gs_comm_create_local", "gs_comm_destroy", "gs_comm_info",
     "gs_cc_merge_window", "gs_cc_fold_windows",
     "gs_last_error", "gs_version",
@@ -95,6 +99,11 @@ class GsCcConfig(ctypes.Structure):
 class GsDegWindowStats(ctypes.Structure):
     _fields_ = [("n_vertices", ctypes.c_uint64), ("n_degrees", ctypes.c_uint64),
                 ("max_degree", ctypes.c_uint64), ("checksum", ctypes.c_uint64)]
+
+
+class GsSliceWindowStats(ctypes.Structure):
+    _fields_ = [("n_vertices", ctypes.c_uint64), ("n_entries", ctypes.c_uint64),
+                ("max_row", ctypes.c_uint64), ("checksum", ctypes.c_uint64)]
 
 
 _LIB: Optional[ctypes.CDLL] = None
@@ -194,6 +203,16 @@ def lib() -> ctypes.CDLL:
         "gs_deg_emit_distribution_delta": [vp, vp, vp, u64, P(u64)],
         "gs_deg_find": [vp, vp, vp, u64],
         "gs_deg_restore": [vp, vp, vp, u64],
+        "gs_slice_create": [P(vp), u64, u32, i32, u32],
+        "gs_slice_destroy": [vp],
+        "gs_slice_set_stream": [vp, vp],
+        "gs_slice_get_stream": [vp, P(vp)],
+        "gs_slice_sync": [vp],
+        "gs_slice_window": [vp, vp, vp, vp, u64],
+        "gs_slice_reduce": [vp, i32, vp, vp, u64, P(u64)],
+        "gs_slice_rows": [vp, vp, vp, vp, vp, u64, u64, P(u64), P(u64)],
+        "gs_slice_stats": [vp, i32, P(GsSliceWindowStats)],
+        "gs_slice_reduce_windows": [vp, vp, vp, vp, u64, u64, i32, vp, vp, u64, vp, vp, u64, P(u64)],
         "gs_comm_unique_id": [vp, u64],
         "gs_comm_create": [P(vp), vp, i32, i32, i32],
         "gs_comm_create_local": [P(vp), i32, i32],

@@ -39,9 +39,9 @@ from .summary import CombineCC, DisjointSet, UpdateCC
 class SimpleEdgeStream:
     """An edge stream in arrival order: src[i] -> dst[i], optional event timestamps (ms) and
     optional event types (``events[i]`` true = EDGE_ADDITION, false = EDGE_DELETION; additions
-    where absent)."""
+    where absent) and optional int64 edge values (``values[i]``, the reference's Long edge value)."""
 
-    def __init__(self, src, dst, timestamps: Optional[Sequence[int]] = None, events=None):
+    def __init__(self, src, dst, timestamps: Optional[Sequence[int]] = None, events=None, values=None):
         self.src = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
         self.dst = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
         if self.src.shape != self.dst.shape:
@@ -52,6 +52,9 @@ class SimpleEdgeStream:
         self.events = None if events is None else np.ascontiguousarray(np.asarray(events).astype(bool).astype(np.uint8))
         if self.events is not None and self.events.shape != self.src.shape:
             raise ValueError("events length mismatch")
+        self.values = None if values is None else np.ascontiguousarray(np.asarray(values, dtype=np.int64))
+        if self.values is not None and self.values.shape != self.src.shape:
+            raise ValueError("values length mismatch")
 
     def __len__(self) -> int:
         return int(self.src.size)
@@ -75,6 +78,13 @@ class SimpleEdgeStream:
         """SimpleEdgeStream.getOutDegrees (:435-438): sources only."""
         from .degrees import degree_stream
         return degree_stream(self, "out", window_edges, **kw)
+
+    def slice(self, time_millis: int = 0, direction: str = "out", *, window_edges: Optional[int] = None, **kw):
+        """SimpleEdgeStream.slice(size, direction) (SimpleEdgeStream.java:135-167): one
+        ``SnapshotStream`` view per window (time windows with timestamps, else count windows of
+        ``window_edges`` edges), each holding the window's neighbourhoods (gsgpu.slices)."""
+        from .slices import slice_stream
+        return slice_stream(self, window_edges, direction, time_millis, **kw)
 
     def windows(self, time_millis: int, window_edges: Optional[int]) -> List[slice]:
         n = len(self)

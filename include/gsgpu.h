@@ -453,6 +453,77 @@ int gs_deg_emit_distribution_delta(gs_deg_t* h, uint32_t* degrees, uint64_t* cou
 int gs_deg_find(gs_deg_t* h, const void* ids, uint32_t* degrees, uint64_t n);
 int gs_deg_restore(gs_deg_t* h, const void* vertices, const uint32_t* degrees, uint64_t n);
 
+/* ---- neighbourhood slices: per-vertex window aggregates over edge values ----
+ * (SimpleEdgeStream.slice(size, direction) -> SnapshotStream, SimpleEdgeStream.java:135-167;
+ *  reduceOnEdges / foldNeighbors / applyOnNeighbors, SnapshotStream.java:61-131)
+ * A count window of n edges (s, d, x), x an int64 edge value (the reference's Long), becomes a
+ * list of entries (key, neighbour, value):
+ *   GS_SLICE_OUT  one per edge: (s, d, x)
+ *   GS_SLICE_IN   one per edge: (d, s, x)                     (reverse())
+ *   GS_SLICE_ALL  two per edge: (s, d, x) at position 2i, then (d, s, x) at 2i + 1   (undirected())
+ * A self-loop (u, u, x) gives u two entries under ALL and one otherwise. The row of a vertex is its
+ * entries IN ARRIVAL ORDER (a keyed window keeps arrival order); a vertex has a row only if it has
+ * an entry in that window. Nothing is kept between windows: the handle holds the last window's
+ * slice and scratch memory. Dense ids in [0, vertex_capacity), vertex_capacity <= 2^32, id_bits 32
+ * or 64, as gs_tri_*. Sparse Long ids and floating-point values are out of scope (a float sum
+ * depends on the order of its terms). Records are emitted ordered by vertex (the reference emits in
+ * no defined order).
+ *   op: reduceOnEdges emits one (vertex, value) per row, the left-to-right reduction of the row's
+ *          values; a row of one entry yields its value unchanged.
+ *          GS_SLICE_SUM    two's-complement wrap, as Java long (foldNeighbors with a summing fold)
+ *          GS_SLICE_MIN / GS_SLICE_MAX   signed
+ *          GS_SLICE_COUNT  entries of the row; the values are ignored and may be absent
+ *          GS_SLICE_FIRST / GS_SLICE_LAST   the reducers (a, b) -> a and (a, b) -> b
+ *   src / dst / val: host or device pointers, as for gs_cc_fold; src / dst id_bits wide. val == NULL
+ *          is allowed with GS_SLICE_COUNT only: any other op on such a slice is GS_ERR_INVALID, and
+ *          gs_slice_rows then writes no values, so its values argument must be NULL too.
+ *   gs_slice_window   builds the slice of one window (it copies what it needs: the caller's arrays
+ *          are free on return). n == 0: GS_OK, an empty slice.
+ *   gs_slice_reduce   reads the slice the last gs_slice_window built; may be called repeatedly
+ *          with different ops. vertices (id_bits wide) and values: host or device arrays of cap
+ *          entries; *n_out = the number of rows; cap < that: GS_ERR_CAPACITY, nothing written.
+ *   gs_slice_rows     the same slice as CSR, what applyOnNeighbors iterates: vertices[nv],
+ *          offsets[nv + 1], neighbours[ne] (id_bits wide), values[ne]; row r is
+ *          offsets[r] .. offsets[r + 1], in arrival order. Host or device arrays; a capacity too
+ *          small: GS_ERR_CAPACITY, nothing written, *n_vertices / *n_entries report the need.
+ *   gs_slice_stats    n_vertices, n_entries, max_row (the longest row) and checksum = sum mod 2^64
+ *          over rows of splitmix64(vertex ^ splitmix64(value ^ 0xD1B54A32D192ED03)), value = the
+ *          row's reduction under op.
+ *   gs_slice_reduce_windows   every window of window_edges edges (the last may be shorter), with
+ *          one host wait, at the end. The records are written concatenated (host or device arrays
+ *          of cap entries); window w is window_offsets[w] .. window_offsets[w + 1]. window_offsets
+ *          (cap_windows + 1 entries) and stats (cap_windows entries, nullable) are host arrays.
+ *          *n_windows = ceil(n / window_edges); cap_windows < that: GS_ERR_CAPACITY, nothing is
+ *          run. Records that outgrow cap: GS_ERR_CAPACITY, nothing is written past cap and the
+ *          outputs are unspecified. Afterwards the handle holds the call's last window.
+ * An id outside [0, vertex_capacity): GS_ERR_RANGE; that window and the later ones of the call
+ * report nothing, and the handle then holds an empty slice. An unknown op or direction:
+ * GS_ERR_INVALID. Limits: a window holds at most 2^30 - 1 edges (positions are 32 bits and the sort
+ * counts entries in an int); above that GS_ERR_UNSUPPORTED, before anything runs. */
+typedef struct gs_slice gs_slice_t;
+enum { GS_SLICE_OUT = 0, GS_SLICE_IN = 1, GS_SLICE_ALL = 2 };
+enum { GS_SLICE_SUM = 0, GS_SLICE_MIN = 1, GS_SLICE_MAX = 2, GS_SLICE_COUNT = 3, GS_SLICE_FIRST = 4, GS_SLICE_LAST = 5 };
+typedef struct gs_slice_window_stats {
+    uint64_t n_vertices;        /* rows of the window */
+    uint64_t n_entries;
+    uint64_t max_row;           /* entries of the longest row */
+    uint64_t checksum;
+} gs_slice_window_stats;
+int gs_slice_create(gs_slice_t** out, uint64_t vertex_capacity, uint32_t id_bits, int device, uint32_t direction);
+int gs_slice_destroy(gs_slice_t* h);          /* NULL is GS_OK */
+int gs_slice_set_stream(gs_slice_t* h, void* hip_stream);
+int gs_slice_get_stream(gs_slice_t* h, void** hip_stream);
+int gs_slice_sync(gs_slice_t* h);
+int gs_slice_window(gs_slice_t* h, const void* src, const void* dst, const int64_t* val, uint64_t n);
+int gs_slice_reduce(gs_slice_t* h, int op, void* vertices, int64_t* values, uint64_t cap, uint64_t* n_out);
+int gs_slice_rows(gs_slice_t* h, void* vertices, uint64_t* offsets, void* neighbours, int64_t* values,
+                  uint64_t cap_vertices, uint64_t cap_entries, uint64_t* n_vertices, uint64_t* n_entries);
+int gs_slice_stats(gs_slice_t* h, int op, gs_slice_window_stats* stats);
+int gs_slice_reduce_windows(gs_slice_t* h, const void* src, const void* dst, const int64_t* val, uint64_t n,
+                            uint64_t window_edges, int op, void* vertices, int64_t* values, uint64_t cap,
+                            uint64_t* window_offsets, gs_slice_window_stats* stats, uint64_t cap_windows,
+                            uint64_t* n_windows);
+
 const char* gs_last_error(void);
 int gs_version(void);
 
